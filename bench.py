@@ -12,7 +12,10 @@ module in training mode (the reference never calls .eval(): batch statistics in 
 independent -> weak scaling: every rank owns its own 64-frame batch, no collective in the data path; the only
 communication is the barrier / max-over-ranks of the timing.
 
-Rank 0 prints ONE JSON line (see MEASUREMENTS.md "Measurement" for the definitions of `roofline` and `cpu_baseline`).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps and prints the headline (`value`,
+`ms_per_step`); --dump-outputs DIR also writes what the last timed step computed.  --full adds everything else after the timed
+region: the self check, rooflines and counters, the other configurations, the CPU baseline (see MEASUREMENTS.md "Measurement"
+for the definitions of `roofline` and `cpu_baseline`).
 """
 from __future__ import annotations
 
@@ -241,7 +244,7 @@ def _summarise_counters(per):
         return "no edge kernel in the counter file"
     steps = sum(rows[k][0] for k in win) / 4.0                       # four conv layers per step (warm-up, probe and timed steps alike)
     how = ("measured in THIS run: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes (kernel trace only) of a child "
-           "`bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-other-configs --no-pcie` started by this process; FETCH doubled on gfx950")
+           "`bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-other-configs --no-pcie` started by this process; FETCH doubled on gfx950")
     LIVE_PMC["pmc_linear_summary.json"] = {"hbm_bytes_per_launch": mean([k for k in rows if wide(k)]), "live": how}
     LIVE_PMC["pmc_mpnn_summary.json"] = {"hbm_bytes_per_launch": mean(win), "edge_kernel": "k_mpnn_win" if win[0].startswith("k_mpnn_win") else "k_mpnn_max",
                                          "live": how}
@@ -273,8 +276,8 @@ def live_traffic(timeout_s=120):
     env = dict(os.environ, TMPDIR="/tmp", RGNN_NO_PLAN_SIDE="1")      # (every kernel alone on the device: the counters mean what they say)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    child = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-other-configs",
-             "--no-pcie", "--no-live-traffic"]
+    child = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline",
+             "--no-other-configs", "--no-pcie", "--no-live-traffic"]
     per = {}
     try:
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
@@ -683,8 +686,15 @@ def self_launch_command(gpus, env, argv, script=None, port=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=_positive_int, default=20, help="timed steps (ms_per_step = their time / steps)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (logits, boxes and the graph the model ran on) "
+                         "as DIR/<name>.npy in float32 / float64; rank 0's batch under a process group")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: self check against an eager pass, repeat blocks, eval-mode and fp32-MFMA "
+                         "steps, rooflines and counters, host streaming, C4 under a process group, the other configurations, the "
+                         "training step and the CPU baseline (the --no-* switches below drop parts of it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--no-pcie", action="store_true", help="skip the host-streaming measurement (loader thread + three streams: rocprofv3 --pmc "
@@ -766,9 +776,11 @@ def main():
         use_graph = a.launch_mode == "graph"
         hot = fr.HotPath(model, settings, use_hip_graphs=use_graph)
     a.hip_graphs = use_graph
+    g = None
     for _ in range(max(a.warmup, 3 if use_graph else 0)):        # >= 3 passes: eager warm-up, graph capture, first replay
         cls, bb, g = hot(batch)
-    g.check()
+    if g is not None:                                            # (--warmup 0 with eager launches: nothing ran yet)
+        g.check()
     sync_all()
     t0 = time.perf_counter()
     for _ in range(a.steps):
@@ -783,6 +795,98 @@ def main():
         per_rank = [FRAMES_PER_GPU * a.steps / float(x.item()) for x in every]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs and rank == 0:                             # (before anything else launches into the timed path's buffers)
+        dump_outputs(a.dump_outputs, cls, bb, g)
+    value = world * FRAMES_PER_GPU * a.steps / elapsed
+    full = None
+    if a.full:                                                   # (after the timed region and the dump)
+        full = full_measurements(a, rank, world, dist, model, settings, batch, frames_list, hot, use_graph, cls, bb, g, sync_all,
+                                 value)
+
+    if rank == 0:
+        line = {
+            "metric": "radar frames/sec (graph-build + GNN fwd)",
+            "value": value, "unit": "frames/s",
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32 (dense layers: fp32 operands split into 2 f16 terms after an exact power-of-two pre-scale, 3 f16 MFMA "
+                     "products per fp32 product, fp32 accumulate -- more accurate than fp32 MFMA against float64, "
+                     "tests/test_gpu_f16x2.py; RGNN_NO_F16X2=1 selects 3 bf16 terms / 6 products, RGNN_LINEAR_FP32=1 "
+                     "v_mfma_f32_32x32x2_f32)",
+            "data": "synthetic",
+            "config": {"workload": "C2: per GPU 64 RadarScenes-shaped frames x 3000 pts, radius graph r=1.0, node feats "
+                                   "[rcs,velocity_vector,time_index,degree], edge feats [relative_position], 4-layer "
+                                   "MPNNConv [224,224,128,64] + emb MLPs + both heads, train-mode BatchNorm, max aggr",
+                       "launch_mode": ("one HIP graph per step (search, features, CSR build and model; edge count verified on the device), replayed"
+                                       if a.hip_graphs else "eager launches on one stream (GPU-bound: launch queue stays ahead), 1 host read of E"),
+                       "launch_mode_probe_ms": {k: round(v * 1e3, 3) for k, v in probes.items()} or None,
+                       "frames_per_gpu": FRAMES_PER_GPU, "points_per_gpu": int(batch.num_points),
+                       "edges_per_gpu": int(g.edge_index.shape[1]), "sharding": "frames, no collective",
+                       "ranks_in_process_group": (dist.get_world_size() if dist is not None else 1),
+                       "per_rank_frames_per_s": per_rank},
+        }
+        if affinity is not None:
+            line["config"]["cpu_affinity_rank0"] = affinity
+        if full is not None:
+            line.update(full)
+    else:
+        line = None
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+    if line is not None:
+        # RCCL prints a version banner through C stdio; flush it (and anything else buffered in libc) BEFORE the result so
+        # that the JSON line is the last line on stdout, then leave without running further native teardown prints
+        import ctypes
+        try:
+            ctypes.CDLL(None).fflush(None)
+        except Exception:
+            pass
+        sys.stdout.flush()
+        print(json.dumps(line), flush=True)
+
+
+def _positive_int(s):
+    v = int(s)
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"expected an integer >= 1, got {s}")
+    return v
+
+
+DUMP_BYTES = 64 << 20        # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, cls, bb, g):
+    """What a caller of the timed path receives from its last step, as <name>.npy: floats as float32, integer tensors (edge
+    index, degree) as float64 (exact).  The C2 outputs fit the budget whole (33 MB); a larger output would be cut to a
+    fixed, seeded sample of its nodes and of its edges, the same rows in every array of one kind."""
+    import numpy as np
+
+    def host(t):
+        v = t.detach().cpu().numpy()
+        return v.astype(np.float32 if v.dtype.kind == "f" else np.float64, copy=False)
+    # name -> (array, what its sampled axis counts, that axis)
+    out = {"logits": (host(cls), "node", 0), "boxes": (host(bb), "node", 0), "node_features": (host(g.x), "node", 0),
+           "edge_index": (host(g.edge_index), "edge", 1), "edge_attr": (host(g.edge_attr), "edge", 0)}
+    if g.degree is not None:
+        out["degree"] = (host(g.degree), "node", 0)
+    total = sum(v.nbytes for v, _, _ in out.values())
+    budget = DUMP_BYTES - 4096 * len(out)                        # (room for the .npy headers)
+    if total > budget:
+        rng = np.random.default_rng(0)
+        keep = {kind: np.sort(rng.choice(n, max(1, n * budget // total), replace=False))
+                for kind, n in (("node", int(cls.shape[0])), ("edge", int(g.edge_index.shape[1])))}
+        out = {k: (np.take(v, keep[kind], axis=ax), kind, ax) for k, (v, kind, ax) in out.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, (v, _, _) in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
+def full_measurements(a, rank, world, dist, model, settings, batch, frames_list, hot, use_graph, cls, bb, g, sync_all, value):
+    """--full: everything after the timed region that the headline does not need.  Runs on every rank (the self check and C4
+    work on all of them); returns, on rank 0, the keys it adds to the headline line (`value`: that line's frames/s)."""
+    from radargnn_amd import frames as fr
+    from radargnn_amd import synthetic
 
     # ---- self check (every rank, after the timed region): what the timed steps left in the output buffers is finite, the
     # device status words are clean, and it equals ONE eager pass over the same batch bit for bit (same kernels, same order;
@@ -867,89 +971,52 @@ def main():
               "frames_per_s_total": world * per / (max(ms) * 1e-3), "per_rank_frames_per_s": [per / (m * 1e-3) for m in ms],
               "ms_per_batch": max(ms) / 16, "ms_per_pass_max_over_ranks": max(ms), "rank0": mine}
 
-    if rank == 0:
-        # instrumented pass: the same steps launched eagerly with HIP events recorded inside librgnn around the two dominant
-        # kernels -- HIP graph replay cannot carry timing events.  Same kernels, same shapes, same stream.
-        summ = instrumented(model, settings, [batch], a.steps, symmetric=True)
-        live_note = None
-        under_profiler = any("rocprof" in os.environ.get(k, "") for k in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "HSA_TOOLS_LIB"))
-        if world == 1 and not a.no_live_traffic and not under_profiler:
-            torch.cuda.synchronize()
-            live_note = live_traffic()                      # (None: measured; else why not -- the line says so)
-        roofline, gather = rooflines(summ, a.steps)
-        line = {
-            "metric": "radar frames/sec (graph-build + GNN fwd)",
-            "value": world * FRAMES_PER_GPU * a.steps / elapsed, "unit": "frames/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32 (dense layers: fp32 operands split into 2 f16 terms after an exact power-of-two pre-scale, 3 f16 MFMA "
-                     "products per fp32 product, fp32 accumulate -- more accurate than fp32 MFMA against float64, "
-                     "tests/test_gpu_f16x2.py; RGNN_NO_F16X2=1 selects 3 bf16 terms / 6 products, RGNN_LINEAR_FP32=1 "
-                     "v_mfma_f32_32x32x2_f32)",
-            "data": "synthetic",
-            "config": {"workload": "C2: per GPU 64 RadarScenes-shaped frames x 3000 pts, radius graph r=1.0, node feats "
-                                   "[rcs,velocity_vector,time_index,degree], edge feats [relative_position], 4-layer "
-                                   "MPNNConv [224,224,128,64] + emb MLPs + both heads, train-mode BatchNorm, max aggr",
-                       "launch_mode": ("one HIP graph per step (search, features, CSR build and model; edge count verified on the device), replayed"
-                                       if a.hip_graphs else "eager launches on one stream (GPU-bound: launch queue stays ahead), 1 host read of E"),
-                       "launch_mode_probe_ms": {k: round(v * 1e3, 3) for k, v in probes.items()} or None,
-                       "frames_per_gpu": FRAMES_PER_GPU, "points_per_gpu": int(batch.num_points),
-                       "edges_per_gpu": int(g.edge_index.shape[1]), "sharding": "frames, no collective",
-                       "ranks_in_process_group": (dist.get_world_size() if dist is not None else 1),
-                       "per_rank_frames_per_s": per_rank},
-            "roofline": roofline,
-            "self_check": self_check,
-        }
-        if repeats is not None:
-            line["value_repeats"] = repeats
-            line["eval_mode"] = eval_mode
-            line["fp32_mfma"] = fp32_line
-        if affinity is not None:
-            line["config"]["cpu_affinity_rank0"] = affinity
-        if c4 is not None:
-            line["c4"] = c4
-        if gather:
-            line["roofline_gather"] = gather
-        line["roofline_search"] = search_roofline(batch, settings, int(g.edge_index.shape[1]))
-        line["step_traffic"] = step_traffic(int(batch.num_points), int(g.edge_index.shape[1]))
-        line["live_traffic"] = ("counters measured in this run (roofline.traffic, roofline_gather.traffic, step_traffic)" if LIVE_PMC else
-                                f"not measured in this run ({live_note or 'switched off, more than one rank, or already under a profiler'}): "
-                                "the committed summaries under profiles/ are quoted")
-        line["bytes_over_survey_compulsory"] = line["step_traffic"]["bytes_over_survey_compulsory"]
-        line["parity_margin"] = parity_margin()
-        if not a.no_pcie:
-            pc = pcie_inclusive(fr.HotPath(model, settings, use_hip_graphs=False), frames_list, max(200, 2 * a.steps))
-            line["pcie_inclusive_value"] = pc["value"]                    # whole window, stalls included
-            line["pcie_inclusive"] = {"batches": pc["batches"], "from_the_median_batch_interval": pc["median_interval_value"],
-                                      "over_resident_value": pc["value"] / line["value"],
-                                      "median_over_resident_value": pc["median_interval_value"] / line["value"],
-                                      "longest_interval_ms": pc["longest_interval_ms"], "slots": pc["slots"],
-                                      "results_behind": pc["results_behind"]}
-        if world == 1 and not a.no_other_configs:
-            line["other_configs"] = other_configs()
-            line["training_step"] = training_step()
-            try:
-                line["other_configs"].append(single_frames_streamed())
-            except Exception as e:                                   # (a side measurement must not cost the line)
-                line["other_configs"].append({"config": "single frames streamed, batch_size = 1", "error": f"{type(e).__name__}: {e}"[:300]})
-        if world == 1 and not a.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(model, settings, a.cpu_frames)
-            line["speedup_vs_cpu_baseline"] = line["value"] / line["cpu_baseline"]["value"]
-    else:
-        line = None
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    if line is not None:
-        # RCCL prints a version banner through C stdio; flush it (and anything else buffered in libc) BEFORE the result so
-        # that the JSON line is the last line on stdout, then leave without running further native teardown prints
-        import ctypes
+    if rank != 0:
+        return None
+    # instrumented pass: the same steps launched eagerly with HIP events recorded inside librgnn around the two dominant
+    # kernels -- HIP graph replay cannot carry timing events.  Same kernels, same shapes, same stream.
+    summ = instrumented(model, settings, [batch], a.steps, symmetric=True)
+    live_note = None
+    under_profiler = any("rocprof" in os.environ.get(k, "") for k in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "HSA_TOOLS_LIB"))
+    if world == 1 and not a.no_live_traffic and not under_profiler:
+        torch.cuda.synchronize()
+        live_note = live_traffic()                      # (None: measured; else why not -- the line says so)
+    roofline, gather = rooflines(summ, a.steps)
+    line = {"roofline": roofline, "self_check": self_check}
+    if repeats is not None:
+        line["value_repeats"] = repeats
+        line["eval_mode"] = eval_mode
+        line["fp32_mfma"] = fp32_line
+    if c4 is not None:
+        line["c4"] = c4
+    if gather:
+        line["roofline_gather"] = gather
+    line["roofline_search"] = search_roofline(batch, settings, int(g.edge_index.shape[1]))
+    line["step_traffic"] = step_traffic(int(batch.num_points), int(g.edge_index.shape[1]))
+    line["live_traffic"] = ("counters measured in this run (roofline.traffic, roofline_gather.traffic, step_traffic)" if LIVE_PMC else
+                            f"not measured in this run ({live_note or 'switched off, more than one rank, or already under a profiler'}): "
+                            "the committed summaries under profiles/ are quoted")
+    line["bytes_over_survey_compulsory"] = line["step_traffic"]["bytes_over_survey_compulsory"]
+    line["parity_margin"] = parity_margin()
+    if not a.no_pcie:
+        pc = pcie_inclusive(fr.HotPath(model, settings, use_hip_graphs=False), frames_list, max(200, 2 * a.steps))
+        line["pcie_inclusive_value"] = pc["value"]                    # whole window, stalls included
+        line["pcie_inclusive"] = {"batches": pc["batches"], "from_the_median_batch_interval": pc["median_interval_value"],
+                                  "over_resident_value": pc["value"] / value,
+                                  "median_over_resident_value": pc["median_interval_value"] / value,
+                                  "longest_interval_ms": pc["longest_interval_ms"], "slots": pc["slots"],
+                                  "results_behind": pc["results_behind"]}
+    if world == 1 and not a.no_other_configs:
+        line["other_configs"] = other_configs()
+        line["training_step"] = training_step()
         try:
-            ctypes.CDLL(None).fflush(None)
-        except Exception:
-            pass
-        sys.stdout.flush()
-        print(json.dumps(line), flush=True)
+            line["other_configs"].append(single_frames_streamed())
+        except Exception as e:                                   # (a side measurement must not cost the line)
+            line["other_configs"].append({"config": "single frames streamed, batch_size = 1", "error": f"{type(e).__name__}: {e}"[:300]})
+    if world == 1 and not a.no_cpu_baseline:
+        line["cpu_baseline"] = cpu_baseline(model, settings, a.cpu_frames)
+        line["speedup_vs_cpu_baseline"] = value / line["cpu_baseline"]["value"]
+    return line
 
 
 if __name__ == "__main__":

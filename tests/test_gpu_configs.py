@@ -148,7 +148,7 @@ def test_bench_runs_under_a_process_group_on_one_gpu():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, RGNN_BENCH_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT="29533")
-    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--full",
                           "--no-cpu-baseline", "--no-other-configs", "--launch-mode", "eager"], env=env, capture_output=True,
                          text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -175,6 +175,38 @@ def test_bench_runs_under_a_process_group_on_one_gpu():
     assert c4["rank0"]["batches"] == 16 and c4["rank0"]["dominant_kernel"]
 
 
+def test_bench_plain_run_dumps_what_the_timed_path_computed(tmp_path):
+    """A plain bench.py run (no --full): the headline keys and nothing measured beside them; --dump-outputs writes the last timed
+    step's logits, boxes and graph, equal bit for bit to one eager pass over the same inputs built in this process."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    from radargnn_amd import frames as fr
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                          "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["value"] > 0 and line["higher_is_better"] is True
+    assert abs(line["ms_per_step"] * line["value"] - 1e3 * bench.FRAMES_PER_GPU) < 1e-6 * line["ms_per_step"] * line["value"]
+    assert {"metric", "unit", "dtype"} <= set(line)
+    assert not {"roofline", "self_check", "cpu_baseline", "other_configs", "pcie_inclusive"} & set(line)
+    model = bench.c2_model().cuda()
+    batch = fr.FrameBatch.from_frames([synthetic.radarscenes_frame(i) for i in range(bench.FRAMES_PER_GPU)])
+    cls, bb, g = fr.HotPath(model, bench.c2_settings(), use_hip_graphs=False)(batch)
+    g.check()
+    want = {"logits": cls, "boxes": bb, "node_features": g.x, "edge_index": g.edge_index, "edge_attr": g.edge_attr, "degree": g.degree}
+    assert sum(os.path.getsize(tmp_path / f"{k}.npy") for k in want) <= 64 << 20
+    for name, t in want.items():
+        a = np.load(tmp_path / f"{name}.npy")
+        assert a.dtype == (np.float32 if t.is_floating_point() else np.float64), name
+        assert np.array_equal(a, t.cpu().numpy()), name
+    assert line["config"]["edges_per_gpu"] == g.edge_index.shape[1]
+
+
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus N` without a launcher starts its N ranks itself (bench.self_launch_command): exercised with the one
     GPU there is -- RGNN_BENCH_SELF_LAUNCH=1 sends --gpus 1 through torch.distributed.run too, and RGNN_BENCH_FORCE_DIST=1 makes the
@@ -186,7 +218,7 @@ def test_bench_launches_its_own_ranks():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(RGNN_BENCH_SELF_LAUNCH="1", RGNN_BENCH_FORCE_DIST="1", MASTER_PORT="29541")
-    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--full",
                           "--no-cpu-baseline", "--no-other-configs", "--no-c4", "--launch-mode", "eager"], env=env, capture_output=True,
                          text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]

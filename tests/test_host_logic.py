@@ -174,6 +174,51 @@ def test_bench_decides_when_to_launch_its_own_ranks():
     assert bench.self_launch_command(1, {"RGNN_BENCH_SELF_LAUNCH": "1"}, ["--gpus", "1"]) is not None   # the launcher path on 1 GPU
 
 
+def test_bench_dump_outputs_writes_the_returned_arrays(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array a caller of the timed path receives, floats as float32 and integers as float64 (exact),
+    whole while they fit the budget, else the same seeded sample of nodes / edges in every array of one kind."""
+    import sys
+    import types
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    n, e = 50, 300
+    gen = torch.Generator().manual_seed(0)
+    g = types.SimpleNamespace(x=torch.randn(n, 5, generator=gen), edge_index=torch.randint(0, n, (2, e), generator=gen),
+                              edge_attr=torch.randn(e, 2, generator=gen), degree=torch.randint(0, 9, (n,), generator=gen, dtype=torch.int32))
+    cls, bb = torch.randn(n, 6, generator=gen), torch.randn(n, 5, generator=gen)
+    bench.dump_outputs(str(tmp_path / "whole"), cls, bb, g)
+    want = {"logits": cls, "boxes": bb, "node_features": g.x, "edge_index": g.edge_index, "edge_attr": g.edge_attr, "degree": g.degree}
+    for name, t in want.items():
+        a = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert a.dtype == (np.float32 if t.is_floating_point() else np.float64), name
+        assert np.array_equal(a, t.numpy()), name
+    monkeypatch.setattr(bench, "DUMP_BYTES", 6 * 4096 + 4000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), cls, bb, g)
+    got = {name: np.load(tmp_path / "a" / f"{name}.npy") for name in want}
+    assert 0 < sum(a.nbytes for a in got.values()) <= 4000
+    assert sum(os.path.getsize(tmp_path / "a" / f"{name}.npy") for name in want) <= bench.DUMP_BYTES
+    for name in want:                                              # a fixed sample: the same rows in every run
+        assert np.array_equal(got[name], np.load(tmp_path / "b" / f"{name}.npy")), name
+    rows = [i for i in range(n) if (cls[i].numpy() == got["logits"]).all(1).any()]
+    assert len(rows) == len(got["logits"]) and np.array_equal(got["boxes"], bb[rows].numpy())
+    assert np.array_equal(got["node_features"], g.x[rows].numpy()) and np.array_equal(got["degree"], g.degree[rows].numpy())
+    cols = [j for j in range(e) if (g.edge_attr[j].numpy() == got["edge_attr"]).all(1).any()]
+    assert len(cols) == len(got["edge_attr"]) and np.array_equal(got["edge_index"], g.edge_index[:, cols].numpy())
+
+
+def test_bench_steps_must_be_positive():
+    import argparse
+    import sys
+    sys.path.insert(0, REPO)
+    import bench
+    assert bench._positive_int("7") == 7
+    for bad in ("0", "-3"):
+        with pytest.raises(argparse.ArgumentTypeError):
+            bench._positive_int(bad)
+
+
 def test_stage_frames_lays_a_batch_out_in_one_block():
     """rgnn_stage_frames (host only): X | V | rcs | timestamp | frame_ptr back to back; empty frames, arrays that need a conversion,
     a block that is too small."""

@@ -5,8 +5,8 @@
   RadarPointGNNConv's residual;
 * an independent float64 numpy restatement (oracle/gnn_numpy.py, one Python iteration per edge) on random graphs, incl.
   DetNetBasic end to end with train-mode BatchNorm, batch_norm_in_mlps and both conv types;
-* if torch_geometric happens to be importable: the reference's own MPNNConv / RadarPointGNNConv / DetNetBasic built from
-  /root/reference/src (self-skipping here: no wheel, no network)."""
+* if torch_geometric happens to be importable: the reference's own MPNNConv / RadarPointGNNConv built from the src/ directory
+  of a reference checkout named by RADARGNN_REFERENCE_SRC (self-skipping without either)."""
 import os
 import sys
 
@@ -137,9 +137,9 @@ def test_det_net_basic_torch_oracle_equals_numpy_oracle(conv_type, aggr, bn_mlps
 # ------------------------------------------------------------------------------------------------ the reference itself, if it can run
 def test_reference_layers_if_torch_geometric_is_present():
     pytest.importorskip("torch_geometric")
-    ref_src = "/root/reference/src"
-    if not os.path.isdir(ref_src):
-        pytest.skip("reference sources not present on this machine")
+    ref_src = os.environ.get("RADARGNN_REFERENCE_SRC", "")
+    if not os.path.isdir(os.path.join(ref_src, "gnnradarobjectdetection")):
+        pytest.skip("RADARGNN_REFERENCE_SRC does not name the src/ directory of a reference checkout")
     # (the repo's gnnradarobjectdetection/ shim must not shadow the reference package for this one test)
     saved = {k: v for k, v in sys.modules.items() if k.startswith("gnnradarobjectdetection")}
     for k in saved:

@@ -11,7 +11,7 @@ win = next(v for k, v in d.items() if "k_mpnn_win" in k)
 steps = win["dispatches"] / 4
 total = sum(v["dispatches"] * v["hbm_bytes_per_launch"] for v in d.values())
 top = sorted(d.items(), key=lambda kv: -kv[1]["dispatches"] * kv[1]["hbm_bytes_per_launch"])[:12]
-out = {"source": f"{src.split('/')[-1]} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes of `bench.py --steps 10 --warmup 3 "
+out = {"source": f"{src.split('/')[-1]} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes of `bench.py --steps 10 --warmup 3 --full "
                  "--no-cpu-baseline --no-other-configs --no-pcie`, FETCH doubled on gfx950; RGNN_NO_PLAN_SIDE=1)",
        "steps_in_the_profiled_command": steps, "hbm_bytes_per_step": total / steps,
        "mb_per_step_by_kernel_top12": {k: round(v["dispatches"] * v["hbm_bytes_per_launch"] / steps / 1e6, 1) for k, v in top}}
