@@ -101,3 +101,119 @@ def det_net_basic_hoisted(x, edge_index, edge_attr, sd: Dict[str, torch.Tensor],
     c = G.run_sequential(x, sd, "classification_head.", training)
     bb = G.run_sequential(x, sd, "regression_head.", training)
     return c.cpu(), bb.cpu()
+
+
+# ---- differentiable form (backward parity at full size) ------------------------------------------------------------------
+# torch's scatter_reduce(amax) splits the gradient of a maximum evenly among tied elements; torch-scatter -- what the reference's
+# layers run on -- and the HIP kernels (csrc/backward.hip) hand ALL of it to the FIRST edge that attains the maximum.  The max
+# stage below therefore records that edge (the lowest edge id: edges are visited in the order the caller lists them) and routes
+# the gradient through it alone.  Mean and add go through plain autograd.
+
+def edge_max(Q: torch.Tensor, We: torch.Tensor, ea: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, n: int, chunk: int = 1 << 18):
+    """-> (M [n, D]: max_e (Q[src_e] + W_e a_e) per target, -inf where a target has no edge; winners int64 [n, D]: the lowest edge id
+    that attains it, -1 where there is none).  Chunks of ``chunk`` edges in ascending id order: a tie across two chunks keeps the
+    earlier chunk's edge."""
+    d = Q.shape[1]
+    M = torch.full((n, d), float("-inf"), dtype=Q.dtype, device=Q.device)
+    win = torch.full((n, d), -1, dtype=torch.int64, device=Q.device)
+    big = torch.iinfo(torch.int64).max
+    for a in range(0, src.numel(), chunk):
+        s, t = src[a:a + chunk], dst[a:a + chunk]
+        v = Q[s] + ea[a:a + chunk] @ We.t()
+        idx = t.view(-1, 1).expand(-1, d)
+        cmax = torch.full((n, d), float("-inf"), dtype=Q.dtype, device=Q.device).scatter_reduce_(0, idx, v, "amax")
+        eid = torch.arange(a, a + s.numel(), device=Q.device).view(-1, 1).expand(-1, d)
+        cand = torch.where(v == cmax[t], eid, torch.full_like(eid, big))
+        cwin = torch.full((n, d), big, dtype=torch.int64, device=Q.device).scatter_reduce_(0, idx, cand, "amin")
+        take = cmax > M                                  # (equal: the earlier chunk's edge has the lower id)
+        M = torch.where(take, cmax, M)
+        win = torch.where(take, cwin, win)
+    return M, win
+
+
+def edge_max_backward(dM: torch.Tensor, We: torch.Tensor, ea: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, n_src: int,
+                      winners: torch.Tensor, chunk: int = 1 << 18):
+    """Gradients of M = edge_max(...) routed through ``winners`` (edge ids per (target, channel); -1: none):
+    -> (dQ [n_src, D], d_edge_attr [E, De], dW_e [D, De]).  dM[t, c] goes to edge winners[t, c] alone."""
+    d = dM.shape[1]
+    dQ = torch.zeros((n_src, d), dtype=dM.dtype, device=dM.device)
+    dea = torch.zeros((src.numel(), ea.shape[1]), dtype=dM.dtype, device=dM.device)
+    dWe = torch.zeros((d, ea.shape[1]), dtype=dM.dtype, device=dM.device)
+    for a in range(0, src.numel(), chunk):
+        s, t = src[a:a + chunk], dst[a:a + chunk]
+        eid = torch.arange(a, a + s.numel(), device=dM.device).view(-1, 1)
+        S = torch.where(winners[t] == eid, dM[t], torch.zeros((), dtype=dM.dtype, device=dM.device))     # [chunk, D]
+        dQ.index_add_(0, s, S)
+        dea[a:a + chunk] = S @ We
+        dWe += S.t() @ ea[a:a + chunk]
+    return dQ, dea, dWe
+
+
+class _EdgeMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Q, We, ea, src, dst, n, chunk, winners):
+        M, win = edge_max(Q, We, ea, src, dst, n, chunk)
+        if winners is not None:
+            win = winners.to(win.device, torch.int64)
+        ctx.save_for_backward(We, ea, src, dst, win)
+        ctx.n_src, ctx.chunk = Q.shape[0], chunk
+        ctx.mark_non_differentiable(win)
+        return M, win
+
+    @staticmethod
+    def backward(ctx, dM, _dwin):
+        We, ea, src, dst, win = ctx.saved_tensors
+        dQ, dea, dWe = edge_max_backward(dM, We, ea, src, dst, ctx.n_src, win, ctx.chunk)
+        return dQ, dWe, dea, None, None, None, None, None
+
+
+def _conv_grad(x, src, dst, deg, ea, sd, prefix, conv_layer_type, aggr, chunk, winners):
+    pre = G._sequential(prefix + "pre_mlp.", sd)
+    if len(pre) != 1:
+        raise NotImplementedError("the hoisted evaluation needs a single-Linear message MLP (pre_layers == 1)")
+    W, b = pre[0][1]["w"], pre[0][1]["b"]
+    n, c = x.shape
+    has = (deg > 0).to(x.dtype).view(-1, 1)
+    if conv_layer_type == "MPNNConv":
+        Wi, Wj, We = W[:, :c], W[:, c:2 * c], W[:, 2 * c:]
+        if prefix + "edge_encoder.weight" in sd:
+            ea = F.linear(ea, sd[prefix + "edge_encoder.weight"], sd[prefix + "edge_encoder.bias"])
+        P = F.linear(x, Wi, b)
+    else:
+        Wj, We = W[:, :c], W[:, c:]
+        P = (b if b is not None else torch.zeros(W.shape[0], dtype=x.dtype, device=x.device)).view(1, -1).expand(n, -1)
+    Q = x @ Wj.t()
+    win = None
+    if aggr == "max":
+        agg, win = _EdgeMax.apply(Q, We, ea, src, dst, n, chunk, winners)
+        m = torch.where(has.bool(), agg + P, torch.zeros((), dtype=x.dtype, device=x.device))
+    else:
+        agg = _edge_stage(Q, We, ea, src, dst, n, aggr, chunk)
+        m = agg / deg.clamp(min=1).to(x.dtype).view(-1, 1) + has * P if aggr == "mean" else agg + deg.to(x.dtype).view(-1, 1) * P
+    h = G.run_sequential(torch.cat([x, m], dim=-1), sd, prefix + "post_mlp.")
+    return (h + x if conv_layer_type != "MPNNConv" else h), win
+
+
+def det_net_basic_hoisted_grad(x, edge_index, edge_attr, sd: Dict[str, torch.Tensor], conv_layer_type: str = "MPNNConv",
+                               aggr: str = "max", training: bool = True, chunk: int = 1 << 18, winners=None, winners_out=None):
+    """``det_net_basic_hoisted`` in a form autograd differentiates: ``x``, ``edge_attr`` and the floating-point entries of ``sd``
+    are used AS GIVEN (their dtype and device; the caller makes them leaves that require gradients), outputs stay where they
+    were computed.  Max aggregation routes every (target, channel) gradient to the lowest edge id attaining the maximum
+    (torch-scatter's rule), or -- ``winners``: a list with one int64 [N, D] tensor of edge ids (or None) per conv layer -- through
+    the given edges.  ``winners_out``: a list that receives the winners each layer used."""
+    src, dst = edge_index[0], edge_index[1]
+    n = x.shape[0]
+    deg = torch.bincount(dst, minlength=n)
+    ea = edge_attr
+    if any(k.startswith("node_emb_mlp.") for k in sd):
+        x = G.run_sequential(x, sd, "node_emb_mlp.", training)
+    if any(k.startswith("edge_emb_mlp.") for k in sd):
+        ea = G.run_sequential(ea, sd, "edge_emb_mlp.", training)
+    n_layers = len({k.split(".")[1] for k in sd if k.startswith("convs.")})
+    for l in range(n_layers):
+        x, win = _conv_grad(x, src, dst, deg, ea, sd, f"convs.{l}.", conv_layer_type, aggr, chunk,
+                            None if winners is None else winners[l])
+        if winners_out is not None:
+            winners_out.append(win)
+        x = torch.relu(G.batch_norm(x, sd, f"batch_norms.{l}.module.", training, update=False))
+    return G.run_sequential(x, sd, "classification_head.", training), G.run_sequential(x, sd, "regression_head.", training)

@@ -34,3 +34,29 @@ def detection_loss(cls: torch.Tensor, bb: torch.Tensor, y: torch.Tensor, bg_inde
     except Exception:
         pass
     return cls_loss_weight * loss_cls + bb_loss_weight * loss_bb, loss_cls, loss_bb
+
+
+def detection_loss_vectorised(cls: torch.Tensor, bb: torch.Tensor, y: torch.Tensor, bg_index: int, class_weights=None,
+                              cls_loss_weight: float = 1.0, bb_loss_weight: float = 1.0, delta: float = 1.0):
+    """``detection_loss`` without the per-node loop, in the dtype and on the device of ``cls`` (differentiable): usable at the
+    10^5 rows of a training batch.  Same function term by term:
+
+    * weighted cross-entropy, mean reduction: sum_i w[y_i] (-log softmax(cls_i)[y_i]) / sum_i w[y_i];
+    * HuberLoss() (mean over the W box components) per row whose label is not ``bg_index``, averaged over those rows;
+    * no such row, or a NaN box term: the box term is 0 (and contributes no gradient)."""
+    label = y[:, 0].long()
+    w = torch.ones(cls.shape[1], dtype=cls.dtype, device=cls.device) if class_weights is None else \
+        torch.as_tensor(class_weights, dtype=cls.dtype).to(cls.device)
+    wi = w[label]
+    nll = -torch.log_softmax(cls, dim=1).gather(1, label.view(-1, 1)).view(-1)
+    loss_cls = (wi * nll).sum() / wi.sum()
+    obj = label != bg_index
+    loss_bb = torch.zeros((), dtype=cls.dtype, device=cls.device)
+    if bool(obj.any()):
+        r = bb[obj] - y[obj, 1:].to(bb.dtype)
+        a = r.abs()
+        h = torch.where(a < delta, 0.5 * r * r, delta * (a - 0.5 * delta))
+        lb = h.mean(dim=1).sum() / int(obj.sum())
+        if not bool(torch.isnan(lb)):
+            loss_bb = lb
+    return cls_loss_weight * loss_cls + bb_loss_weight * loss_bb, loss_cls, loss_bb

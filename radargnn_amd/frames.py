@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .gnn import autograd as AG
 from .gnn.linear import frame_scope
 from .gnn.mpnn_layers import TargetCSR
 from .synthetic import RadarFrame, concat_frames
@@ -313,12 +314,21 @@ class HotPath:
         # radius graphs hold (s, t) and (t, s) alike (|a - b|^2 is evaluated symmetrically); kNN graphs do not
         self.symmetric_graph = graph_settings.algorithm == "radius"
         # a maximum does not depend on the order of a target's in-edges: the CSR build of kNN batches skips its ranking pass
-        self._ordered_csr = not (getattr(model, "aggregation", None) == "max" and os.environ.get("RGNN_ORDERED_CSR") is None)
+        # (inference only: see _ordered_csr)
+        self._unordered_csr_ok = getattr(model, "aggregation", None) == "max" and os.environ.get("RGNN_ORDERED_CSR") is None
         self._seen = None          # id of the batch seen last (first sight runs eagerly)
         self._seen_edges = 0       # ... and the edge count that pass found
         self._key = None           # signature of the captured graph
         self._graph = None
         self._static = None        # static buffers of the search stage + outputs of the captured graph
+
+    @property
+    def _ordered_csr(self) -> bool:
+        """Decided where a CSR is built, not once per HotPath: the VALUE of a maximum does not depend on the order of a target's
+        in-edges, but its gradient goes to the FIRST in-edge that attains it -- under exact ties (duplicate points) the unordered
+        build would hand it to whichever edge the build's atomics put first.  So the unordered build only when no gradient is being
+        recorded (a step run under gnn.autograd.recording(): the model's differentiable form)."""
+        return not self._unordered_csr_ok or (torch.is_grad_enabled() and AG.is_recording())
 
     # ---- the two halves of a step -------------------------------------------------------------------
     def _model(self, g: GraphBatch):

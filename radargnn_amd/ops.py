@@ -1625,12 +1625,16 @@ def bn_bwd_apply(dy: torch.Tensor, y: Optional[torch.Tensor], h: torch.Tensor, c
 
 
 def mpnn_aggregate_bwd(dM, Q, We, ea_sorted, rowptr_t, src_sorted, aggr: str, source_csr, node_order=None,
-                       target_scale: Optional[torch.Tensor] = None, edge_maps=None, arg: Optional[torch.Tensor] = None):
+                       target_scale: Optional[torch.Tensor] = None, edge_maps=None, arg: Optional[torch.Tensor] = None,
+                       arg_out: Optional[torch.Tensor] = None):
     """Gradients of M[t] = aggr_{e->t}(Q[src_e] + We a_e) -> (dQ [n,d], d_edge_attr [E,de] or None, dWe [d,de] or None).
     ``source_csr`` = (rowptr_s, tnode, tpos): the same edges keyed on their source (see rgnn.h).  ``edge_maps`` =
     (tgt_sorted, eloc_sorted, tloc) -- target and in-segment index of every sorted edge, in-segment index of every out-edge
     (TargetCSR.edge_maps(); None when an in-degree exceeds 65 535) -- enables the lane-local kernels of rgnn_mpnn_max_bwd on
-    the shapes they cover; ``arg``: the winners the forward pass recorded (uint16 in-segment indices; else recomputed)."""
+    the shapes they cover; ``arg``: the winners the forward pass recorded (uint16 in-segment indices; else recomputed).
+    ``arg_out`` (tests: which edges the gradient went to): a caller-owned [n, d] buffer the launch recomputes its winners into,
+    int32 CSR positions on the generic kernel, int16 (uint16) in-segment indices on the lane-local one; not written when ``arg``
+    is given or the aggregation is not max."""
     dM = _rowmajor(_dev(dM, "dM", torch.float32), "dM")
     _, Q, We, ea_sorted, de = _mp_common(None, None, Q, We, ea_sorted, rowptr_t, src_sorted)
     n, d = rowptr_t.numel() - 1, Q.shape[1]
@@ -1655,6 +1659,8 @@ def mpnn_aggregate_bwd(dM, Q, We, ea_sorted, rowptr_t, src_sorted, aggr: str, so
         have_arg = arg is not None
         if have_arg:
             _dev(arg, "arg", torch.int16)
+        elif arg_out is not None:
+            arg = _arg_buffer(arg_out, n, d, torch.int16)
         else:
             arg = torch.empty((n, d), dtype=torch.int16, device=dev)
         word = ctx().bounds.word() if ctx().bounds is not None else None  # max |dQ|: the dx launch reads [dh | dQ] (f16x2 form)
@@ -1669,7 +1675,9 @@ def mpnn_aggregate_bwd(dM, Q, We, ea_sorted, rowptr_t, src_sorted, aggr: str, so
     dea_part = torch.empty((cs, n_edges, de), dtype=torch.float32, device=dev) if (de and cs > 1) else None
     dWe = torch.empty((d, de), dtype=torch.float32, device=dev) if de else None
     part = torch.empty((int(lib.rgnn_mpnn_bwd_slots(n)), d, de), dtype=torch.float32, device=dev) if de else None
-    arg = torch.empty((n, d), dtype=torch.int32, device=dev) if AGGR_CODES[aggr] == 0 else None
+    arg = None
+    if AGGR_CODES[aggr] == 0:
+        arg = torch.empty((n, d), dtype=torch.int32, device=dev) if arg_out is None else _arg_buffer(arg_out, n, d, torch.int32)
     if AGGR_CODES[aggr] == 1:
         _dev(target_scale, "target_scale", torch.float32)
     check(lib.rgnn_mpnn_aggregate_bwd(_ptr(dM), _ld(dM), _ptr(Q), _ld(Q), _ptr(We), 0 if We is None else _ld(We),
@@ -1678,6 +1686,13 @@ def mpnn_aggregate_bwd(dM, Q, We, ea_sorted, rowptr_t, src_sorted, aggr: str, so
                                       n_edges, _ptr(arg), _ptr(part), _ptr(dea_part), _ptr(dQ), d, _ptr(dea), _ptr(dWe),
                                       _stream()))
     return dQ, dea, dWe
+
+
+def _arg_buffer(t: torch.Tensor, n: int, d: int, dtype) -> torch.Tensor:
+    _dev(t, "arg_out", dtype)
+    if tuple(t.shape) != (n, d) or not t.is_contiguous():
+        raise ValueError(f"arg_out must be a contiguous [{n}, {d}] {dtype} tensor")
+    return t
 
 
 def linear_wgrad_supported(g: torch.Tensor, a1: torch.Tensor, a2: Optional[torch.Tensor]) -> bool:
