@@ -734,6 +734,32 @@ int rgnn_box_representations(const double* corners, int64_t m, double* two_point
 int rgnn_nms(const void* boxes, int32_t kind, const int64_t* order, int64_t m, double iou_threshold, uint64_t* mask_tmp,
              int64_t* keep, int64_t* count, rgnn_stream_t stream);
 
+/* ================================================================ evaluation: ground truth and point IoU
+ * Ground-truth boxes of one graph / batch (GroundTruthExtractor.get_absolute_object_bounding_boxes,
+ * postprocessor/postprocessing.py:447-551): keep = (labels[i * ldl] != bg_index) (float32 labels, NaN kept) and the four
+ * corners of every node's absolute box, the box algebra of rgnn_decode_predictions without the angle adaption.
+ * keep: [dev] int32 [n]; corners: [dev] float64 [n, 4, 2]. */
+int rgnn_decode_ground_truth(const float* labels, int64_t ldl, const float* boxes, int64_t ldb, int32_t box_width,
+                             const float* pos, const int32_t* nn_index, int64_t n, int32_t bg_index, int32_t invariance,
+                             int32_t* keep, double* corners, rgnn_stream_t stream);
+/* Duplicate ground-truth boxes (GroundTruthExtractor.remove_duplicate_boxes, postprocessing.py:552-575): box j of a frame
+ * is dropped iff some box i < j of the same frame (dropped or not) has all 8 corners == or a float64 sum of the 8 absolute
+ * differences (numpy's pairwise order) < 0.1.  corners: [dev] float64 [m, 4, 2]; box_ptr: [dev] int64 [n_frames + 1] box
+ * offsets of the frames; keep: [dev] int32 [m], 1 = kept. */
+int rgnn_remove_duplicate_boxes(const double* corners, const int64_t* box_ptr, int64_t n_frames, int64_t m, int32_t* keep,
+                                rgnn_stream_t stream);
+/* Point IoU matrices of a batch of frames (point_iou, utils/math.py:176-211): for frame f, iou[out_ptr[f] + p * G_f + g]
+ * (float64, row-major [P_f, G_f]) of predicted box p and ground-truth box g: tp = distinct (x, y) coordinates inside both,
+ * fp / fn = points inside one box minus tp, tp / (tp + fp + fn) or 0.00001 when that is 0.  Boxes float32: aligned
+ * [x_min, y_min, x_max, y_max] (rotated = 0) or [x, y, l, w, theta in degrees] (rotated = 1, is_point_in_rect's area test
+ * in float64); pred_ptr / gt_ptr / frame_ptr / out_ptr: [dev] int64 [n_frames + 1] offsets of the boxes, of the points
+ * (float32 [N, 2]) and of the matrices (n_out = out_ptr[n_frames]); max_frame_points: the largest frame, at most 8192;
+ * tmp: [dev] rgnn_point_iou_tmp_bytes(n_frames, ceil(max_frame_points / 64), n_pred, n_gt) bytes. */
+int64_t rgnn_point_iou_tmp_bytes(int64_t n_frames, int32_t words, int64_t n_pred, int64_t n_gt);
+int rgnn_point_iou(const float* boxes_pred, const int64_t* pred_ptr, int64_t n_pred, const float* boxes_gt, const int64_t* gt_ptr,
+                   int64_t n_gt, int32_t rotated, const float* points, const int64_t* frame_ptr, int64_t n_frames,
+                   int32_t max_frame_points, const int64_t* out_ptr, int64_t n_out, double* iou, void* tmp, rgnn_stream_t stream);
+
 /* ================================================================ backward pass (training: gnn/trainer.py:176-231)
  * What autograd derives for the reference's op-by-op forward, for the fused forward kernels above.  The dense-layer
  * gradients are GEMMs: dX = dY W runs on rgnn_linear_fwd with the transposed weight, dW = dY^T X on rgnn_wgrad

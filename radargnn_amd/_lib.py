@@ -174,6 +174,10 @@ SIGNATURES = {
     "rgnn_sort_scores": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_vp, c_vp]),
     "rgnn_nms_mask_words": (c_i64, [c_i64]),
     "rgnn_nms": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_f64, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_decode_ground_truth": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "rgnn_remove_duplicate_boxes": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
+    "rgnn_point_iou_tmp_bytes": (c_i64, [c_i64, c_i32, c_i64, c_i64]),
+    "rgnn_point_iou": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "rgnn_detection_loss_blocks": (c_i64, [c_i64]),
     "rgnn_detection_loss": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_i32, c_f32, c_f32, c_f32,
                                     c_vp, c_vp, c_vp, c_vp]),

@@ -32,46 +32,33 @@ struct DecodeParams {
 
 __device__ __forceinline__ double round5(double x) { return rint(x * 100000.0) / 100000.0; }   // np.round(x, 5)
 
-__global__ __launch_bounds__(256) void k_decode(const DecodeParams p) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= p.n) return;
-  const float* pr = p.prob + i * p.ldp;
-  int best = 0;
-  float m = pr[0];
-  for (int k = 1; k < p.K; k++) {
-    const float v = pr[k];
-    if (v > m) { m = v; best = k; }                     // np.where(vec == max)[0][0]: the first maximum
-  }
-  bool remove = false;
-  if (p.bg_index >= 0 && p.bg_index < p.K) remove = pr[p.bg_index] >= p.max_bg;     // postprocessing.py:222
-  remove = remove || best == p.bg_index;                                            // :223
-  if (best < p.n_min) remove = remove || ((double)m <= p.min_score[best]);          // :227-228
-  p.label[i] = best;
-  p.score[i] = m;
-  p.keep[i] = remove ? 0 : 1;
-
-  const float* b = p.bb + i * p.ldb;
-  const double px = (double)p.pos[2 * i], py = (double)p.pos[2 * i + 1];
+// The absolute box of node i (box algebra of preprocessor/bounding_box.py, see the head of this file): corners c1..c4
+// (x, y) in float64 into corners[8 i ..].  Shared by the prediction and the ground-truth decode.
+__device__ __forceinline__ void decode_box(const float* __restrict__ bb, int64_t ldb, int W, const float* __restrict__ pos,
+                                           const int32_t* __restrict__ nn, int invariance, int adapt_angle, int64_t i,
+                                           double* __restrict__ corners) {
+  const float* b = bb + i * ldb;
+  const double px = (double)pos[2 * i], py = (double)pos[2 * i + 1];
   double cx, cy, hl, hw, theta_deg = 0.0;
   bool rotate = false;
-  if (p.W == 4) {                                        // relative aligned box: bounding_box.py:275-312
+  if (W == 4) {                                        // relative aligned box: bounding_box.py:275-312
     cx = px + (double)b[0]; cy = py + (double)b[1];
     hl = (double)b[2] / 2; hw = (double)b[3] / 2;
-  } else if (p.invariance != 2) {
+  } else if (invariance != 2) {
     hl = (double)b[2] / 2; hw = (double)b[3] / 2;
     double th = (double)b[4];
-    if (p.adapt_angle) {                                 // invert_bb_orientation_angle_adaption, bounding_box.py:566-589
+    if (adapt_angle) {                                 // invert_bb_orientation_angle_adaption, bounding_box.py:566-589
       th = fmax(fmin(th, 1.0), -1.0);
       th = asin(th);
       if (th < 0) th = th + PI_D;
     }
     theta_deg = th * 180 / PI_D;
     rotate = true;
-    if (p.invariance == 1) { cx = px + (double)b[0]; cy = py + (double)b[1]; }      // relative rotated :156-199
+    if (invariance == 1) { cx = px + (double)b[0]; cy = py + (double)b[1]; }      // relative rotated :156-199
     else { cx = (double)b[0]; cy = (double)b[1]; }                                  // absolute rotated :21-66
   } else {                                               // E(n)-invariant representation: bounding_box.py:97-153
-    const int32_t j = p.nn[i];
-    const double vx = (double)p.pos[2 * (int64_t)j] - px, vy = (double)p.pos[2 * (int64_t)j + 1] - py;
+    const int32_t j = nn[i];
+    const double vx = (double)pos[2 * (int64_t)j] - px, vy = (double)pos[2 * (int64_t)j + 1] - py;
     const double nrm = sqrt(vx * vx + vy * vy);
     const double th_nn = atan2(vy / nrm, vx / nrm) * 180 / PI_D;
     const double d = (double)b[0];
@@ -93,7 +80,7 @@ __global__ __launch_bounds__(256) void k_decode(const DecodeParams p) {
     c = cos(rad); s = sin(rad);
   }
   const double ox[4] = {hl, hl, -hl, -hl}, oy[4] = {hw, -hw, -hw, hw};              // c1..c4 before rotation
-  double* out = p.corners + i * 8;
+  double* out = corners + i * 8;
 #pragma unroll
   for (int q = 0; q < 4; q++) {
     const double rx = rotate ? c * ox[q] + (-s) * oy[q] : ox[q];
@@ -101,6 +88,40 @@ __global__ __launch_bounds__(256) void k_decode(const DecodeParams p) {
     out[2 * q] = rx + cx;
     out[2 * q + 1] = ry + cy;
   }
+}
+
+__global__ __launch_bounds__(256) void k_decode(const DecodeParams p) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.n) return;
+  const float* pr = p.prob + i * p.ldp;
+  int best = 0;
+  float m = pr[0];
+  for (int k = 1; k < p.K; k++) {
+    const float v = pr[k];
+    if (v > m) { m = v; best = k; }                     // np.where(vec == max)[0][0]: the first maximum
+  }
+  bool remove = false;
+  if (p.bg_index >= 0 && p.bg_index < p.K) remove = pr[p.bg_index] >= p.max_bg;     // postprocessing.py:222
+  remove = remove || best == p.bg_index;                                            // :223
+  if (best < p.n_min) remove = remove || ((double)m <= p.min_score[best]);          // :227-228
+  p.label[i] = best;
+  p.score[i] = m;
+  p.keep[i] = remove ? 0 : 1;
+
+  decode_box(p.bb, p.ldb, p.W, p.pos, p.nn, p.invariance, p.adapt_angle, i, p.corners);
+}
+
+// Ground truth (GroundTruthExtractor.get_absolute_object_bounding_boxes, postprocessor/postprocessing.py:447-551): a node
+// is kept when its label (float32) != bg_index; no score filter, and the angle is never adapted.
+__global__ __launch_bounds__(256) void k_decode_ground_truth(const float* __restrict__ labels, int64_t ldl,
+                                                             const float* __restrict__ bb, int64_t ldb, int W,
+                                                             const float* __restrict__ pos, const int32_t* __restrict__ nn,
+                                                             int64_t n, int bg_index, int invariance, int32_t* __restrict__ keep,
+                                                             double* __restrict__ corners) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  keep[i] = (double)labels[i * ldl] != (double)bg_index ? 1 : 0;     // np.where(class_labels == bg_index): NaN is kept
+  decode_box(bb, ldb, W, pos, nn, invariance, 0, i, corners);
 }
 
 }  // namespace
@@ -120,6 +141,21 @@ extern "C" int rgnn_decode_predictions(const float* class_prob, int64_t ldp, int
   DecodeParams p{class_prob, ldp, n_classes, boxes, ldb, box_width, pos, nn_index, n, bg_index, max_score_for_background,
                  min_object_score, n_min_scores, invariance, adapt_orientation_angle, label, score, keep, corners};
   hipLaunchKernelGGL(k_decode, dim3(rgnn_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, p);
+  RGNN_CHECK_LAUNCH();
+  return RGNN_OK;
+}
+
+extern "C" int rgnn_decode_ground_truth(const float* labels, int64_t ldl, const float* boxes, int64_t ldb, int32_t box_width,
+                                        const float* pos, const int32_t* nn_index, int64_t n, int32_t bg_index,
+                                        int32_t invariance, int32_t* keep, double* corners, rgnn_stream_t stream) {
+  RGNN_CHECK_ARG(n >= 0, "bad sizes");
+  RGNN_CHECK_ARG(box_width == 4 || box_width == 5, "boxes are [x, y, dx, dy] or [x, y, l, w, theta]");
+  RGNN_CHECK_ARG(invariance >= 0 && invariance <= 2, "invariance: 0 none, 1 translation, 2 en");
+  if (n == 0) return RGNN_OK;
+  RGNN_CHECK_ARG(!(invariance == 2 && box_width == 5) || nn_index != nullptr, "the en representation needs nearest neighbours");
+  RGNN_CHECK_ARG(labels && boxes && pos && keep && corners, "null pointers");
+  hipLaunchKernelGGL(k_decode_ground_truth, dim3(rgnn_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, labels, ldl, boxes, ldb,
+                     (int)box_width, pos, nn_index, n, (int)bg_index, (int)invariance, keep, corners);
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
 }

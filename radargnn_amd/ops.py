@@ -1906,6 +1906,70 @@ def nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float, rotated
     return keep[:int(count.item())]
 
 
+# ---- evaluation: ground truth, duplicate removal, point IoU (csrc/postprocess.hip, csrc/evaluate.hip) ----------------
+def decode_ground_truth(labels: torch.Tensor, boxes: torch.Tensor, pos: torch.Tensor, nn_index: Optional[torch.Tensor],
+                        bg_index: int, invariance: int):
+    """-> (keep int32 [N] (label != bg_index), corners f64 [N, 4, 2]) (rgnn_decode_ground_truth).  ``labels``: float32 [N],
+    any stride (a column of ``y``)."""
+    _dev(labels, "labels", torch.float32)
+    boxes = _rowmajor(_dev(boxes, "boxes", torch.float32), "boxes")
+    _dev(pos, "pos", torch.float32)
+    if not pos.is_contiguous():
+        raise ValueError("pos must be contiguous [N, 2]")
+    n = boxes.shape[0]
+    if labels.dim() != 1 or labels.shape[0] != n:
+        raise ValueError("labels must be [N]")
+    if nn_index is not None:
+        _dev(nn_index, "nn_index", torch.int32)
+    keep = torch.empty(n, dtype=torch.int32, device=boxes.device)
+    corners = torch.empty((n, 4, 2), dtype=torch.float64, device=boxes.device)
+    check(lib.rgnn_decode_ground_truth(_ptr(labels), labels.stride(0) if n > 1 else 1, _ptr(boxes),
+                                       _ld(boxes) if n > 1 else boxes.shape[1], boxes.shape[1], _ptr(pos), _ptr(nn_index), n,
+                                       int(bg_index), int(invariance), _ptr(keep), _ptr(corners), _stream()))
+    return keep, corners
+
+
+def remove_duplicate_boxes(corners: torch.Tensor, box_ptr: torch.Tensor) -> torch.Tensor:
+    """corners f64 [M, 4, 2], box_ptr int64 [B + 1] box offsets of the frames -> keep int32 [M] (rgnn_remove_duplicate_boxes)."""
+    corners = _dev(corners, "corners", torch.float64).contiguous()
+    box_ptr = _dev(box_ptr, "box_ptr", torch.int64).contiguous()
+    m = corners.shape[0]
+    keep = torch.empty(m, dtype=torch.int32, device=corners.device)
+    check(lib.rgnn_remove_duplicate_boxes(_ptr(corners), _ptr(box_ptr), box_ptr.numel() - 1, m, _ptr(keep), _stream()))
+    return keep
+
+
+def point_iou(boxes_pred: torch.Tensor, pred_ptr: Sequence[int], boxes_gt: torch.Tensor, gt_ptr: Sequence[int],
+              points: torch.Tensor, frame_ptr: Sequence[int], rotated: bool):
+    """Point IoU matrices of a batch of frames (rgnn_point_iou) -> (iou f64 [sum P_f G_f], matrix offsets [B + 1] as a list).
+    ``boxes_*``: float32 [M, 4] aligned or [M, 5] rotated; ``points`` float32 [N, 2]; the offsets (host sequences of B + 1
+    ints) split boxes and points into frames.  Frame f's matrix is ``iou[out[f]:out[f + 1]].view(P_f, G_f)``."""
+    width = 5 if rotated else 4
+    boxes_pred = _dev(boxes_pred, "boxes_pred", torch.float32).contiguous()
+    boxes_gt = _dev(boxes_gt, "boxes_gt", torch.float32).contiguous()
+    points = _dev(points, "points", torch.float32).contiguous()
+    pp, gp, fp = [int(v) for v in pred_ptr], [int(v) for v in gt_ptr], [int(v) for v in frame_ptr]
+    b = len(fp) - 1
+    if b < 1 or len(pp) != b + 1 or len(gp) != b + 1:
+        raise ValueError("pred_ptr, gt_ptr and frame_ptr need one offset per frame plus one")
+    if boxes_pred.dim() != 2 or boxes_pred.shape[1] != width or boxes_gt.dim() != 2 or boxes_gt.shape[1] != width:
+        raise ValueError(f"boxes must be [M, {width}] for {'rotated' if rotated else 'aligned'} boxes")
+    if pp[-1] != boxes_pred.shape[0] or gp[-1] != boxes_gt.shape[0] or fp[-1] != points.shape[0] or points.shape[1:] != (2,):
+        raise ValueError("the offsets must end at the number of boxes / points; points are [N, 2]")
+    out = [0]
+    for f in range(b):
+        out.append(out[-1] + (pp[f + 1] - pp[f]) * (gp[f + 1] - gp[f]))
+    max_points = max(fp[f + 1] - fp[f] for f in range(b))
+    dev = points.device
+    iou = torch.empty(out[-1], dtype=torch.float64, device=dev)
+    ptrs = torch.tensor([pp, gp, fp, out], dtype=torch.int64).to(dev)
+    words = (max_points + 63) // 64
+    tmp = torch.empty(max(int(lib.rgnn_point_iou_tmp_bytes(b, words, pp[-1], gp[-1])), 8), dtype=torch.uint8, device=dev)
+    check(lib.rgnn_point_iou(_ptr(boxes_pred), _ptr(ptrs[0]), pp[-1], _ptr(boxes_gt), _ptr(ptrs[1]), gp[-1], 1 if rotated else 0,
+                             _ptr(points), _ptr(ptrs[2]), b, max_points, _ptr(ptrs[3]), out[-1], _ptr(iou), _ptr(tmp), _stream()))
+    return iou, out
+
+
 # ---- detection loss (csrc/loss.hip) ----------------------------------------------------------------------------------
 def detection_loss(cls: torch.Tensor, boxes: torch.Tensor, y: torch.Tensor, class_weight: Optional[torch.Tensor],
                    bg_index: int, delta: float, cls_loss_weight: float, bb_loss_weight: float):

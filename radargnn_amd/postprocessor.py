@@ -6,6 +6,11 @@ from ``frames.HotPath`` / the model heads, nothing leaves the device); results s
 
 The E(n)-invariant box representation needs every point's nearest neighbour: the k = 1 use of the kNN kernel
 (``ops.knn_graph``) instead of sklearn + a dense N x N ``toarray()`` (postprocessing.py:233-237).
+
+The evaluation half: ``GroundTruthExtractor`` (ground-truth decode + duplicate removal, postprocessing.py:438-575),
+``Postprocessor.process`` over whole lists of frames (one decode launch per half, one duplicate-removal launch; only NMS
+runs frame by frame) and the point IoU of ``utils/math.py:176-211`` (``point_iou``, ``point_iou_batched``) on
+``rgnn_decode_ground_truth`` / ``rgnn_remove_duplicate_boxes`` / ``rgnn_point_iou``.
 """
 from __future__ import annotations
 
@@ -142,6 +147,14 @@ class PredictionExtractor:
                 score.index_select(0, idx).to(torch.float64).view(-1, 1),
                 label.index_select(0, idx).to(torch.float64).view(-1, 1))
 
+    def extract(self, predictions: Dict) -> List[torch.Tensor]:
+        """postprocessing.py:321-333: the predicted label [N, 1] (float64) of every node of every graph; one launch for all."""
+        frames = predictions.get("class_probability_prediction")
+        prob = _concat(frames, "class_probability_prediction")
+        label, _ = ops.row_argmax(prob)
+        label = label.to(torch.float64).view(-1, 1)
+        sizes = [int(torch.as_tensor(f).shape[0]) for f in frames]
+        return list(torch.split(label, sizes)) if sizes else []
 
 class BoxSuppressor:
     """postprocessor/postprocessing.py:336-431: non-maximum suppression of one graph's decoded boxes, rotated
@@ -181,8 +194,9 @@ class BoxSuppressor:
 
 
 class Postprocessor:
-    """postprocessor/postprocessing.py:14-79 (the prediction half): decode + NMS + the per-node segmentation outputs, as the
-    two dicts the reference returns -- values are tensors in HBM instead of numpy arrays."""
+    """postprocessor/postprocessing.py:14-163: decode + NMS + the per-node segmentation outputs of the predictions, the
+    ground-truth boxes without duplicates, as the dicts the reference returns -- values are tensors in HBM instead of numpy
+    arrays."""
 
     @staticmethod
     def process_one_raw_prediction(config: PostProcessingConfiguration, pos, raw_bb_pred, raw_cls_prob_pred):
@@ -203,6 +217,62 @@ class Postprocessor:
         return detection, segmentation
 
     @staticmethod
+    def process_one_ground_truth(pos, vel, raw_bb_ground_truth, raw_cls_ground_truth, bb_invariance: str, bg_index: int):
+        """postprocessing.py:81-118: ground-truth boxes of one graph without duplicates, and the ground-truth segmentation."""
+        boxes, labels = GroundTruthExtractor.get_absolute_object_bounding_boxes(raw_cls_ground_truth, raw_bb_ground_truth, pos,
+                                                                                bb_invariance, bg_index)
+        boxes, labels = GroundTruthExtractor.remove_duplicate_boxes(boxes, labels)
+        objects = {"boxes": boxes, "labels": labels[:, 0]}
+        segmentation = {"pos": _f32_cuda(pos, "pos"), "vel": None if vel is None else _cuda(vel, "vel", None),
+                        "labels": _cuda(raw_cls_ground_truth, "class_true", None)}
+        return objects, segmentation
+
+    def process(self, config: PostProcessingConfiguration, raw_pos, raw_vel, predictions: Dict, ground_truth: Dict):
+        """postprocessing.py:120-163 over lists of graphs (numpy, as ``Predictor.predict`` returns them, or CUDA tensors):
+        -> (bb_pred, bb_ground_truth, cls_pred, cls_ground_truth), lists of dicts with the reference's keys.  One decode launch
+        per half over all graphs, one duplicate-removal launch; NMS frame by frame."""
+        raw_bb_pred = predictions.get("bounding_box_predictions")
+        raw_cls_prob_pred = predictions.get("class_probability_prediction")
+        raw_bb_gt = ground_truth.get("bounding_box_true")
+        raw_cls_gt = ground_truth.get("class_true")
+        frames = [raw_pos, raw_bb_pred, raw_cls_prob_pred, raw_bb_gt, raw_cls_gt]
+        n_frames = len(raw_pos)
+        if any(len(f) != n_frames for f in frames) or (raw_vel is not None and len(raw_vel) != n_frames):
+            raise ValueError("positions, velocities, predictions and ground truth need one entry per graph")
+        if n_frames == 0:
+            return [], [], [], []
+        ptr = [0]
+        for p in raw_pos:
+            ptr.append(ptr[-1] + int(torch.as_tensor(p).shape[0]))
+        pos = _concat(raw_pos, "pos")
+        bb_pred, cls_prob = _concat(raw_bb_pred, "bounding_box_predictions"), _concat(raw_cls_prob_pred, "class_probability_prediction")
+        bb_gt = _concat(raw_bb_gt, "bounding_box_true")
+        labels_gt = _concat([_labels_column(c) for c in raw_cls_gt], "class_true", None)
+        nn_index = _nearest_in_frames(pos, ptr) if config.bb_invariance == "en" else None
+
+        # predictions: one decode launch, suppression per graph
+        label, score, keep, corners = decode(cls_prob, bb_pred, pos, config, nn_index=nn_index)
+        aligned_pred = bb_pred.shape[1] == 4
+        bb_out, cls_out = [], []
+        for a, b in zip(ptr[:-1], ptr[1:]):
+            det, seg = Postprocessor._finish(config, pos[a:b], cls_prob[a:b], label[a:b], score[a:b], keep[a:b], corners[a:b],
+                                             aligned_pred)
+            bb_out.append(det)
+            cls_out.append(seg)
+
+        # ground truth: one decode launch, one duplicate-removal launch
+        gt_corners, gt_labels, box_ptr = _ground_truth(labels_gt, bb_gt, pos, ptr, config.bb_invariance, config.bg_index, nn_index)
+        bounds = box_ptr.cpu().tolist()
+        aligned_gt = bb_gt.shape[1] == 4
+        gt_out, gt_seg = [], []
+        for f in range(n_frames):
+            a, b = bounds[f], bounds[f + 1]
+            gt_out.append({"boxes": BoundingBoxes(gt_corners[a:b], aligned_gt), "labels": gt_labels[a:b]})
+            vel = None if raw_vel is None else _cuda(raw_vel[f], "vel", None)
+            gt_seg.append({"pos": pos[ptr[f]:ptr[f + 1]], "vel": vel, "labels": labels_gt[ptr[f]:ptr[f + 1]]})
+        return bb_out, gt_out, cls_out, gt_seg
+
+    @staticmethod
     def process_batch(config: PostProcessingConfiguration, pos, raw_bb_pred, raw_cls_prob_pred, ptr):
         """The same for a whole batch straight from the model (``Batch.ptr`` / ``FrameBatch.frame_ptr`` node offsets): ONE
         decode launch over all nodes (nearest neighbours for the "en" boxes searched per frame), then suppression frame by
@@ -219,3 +289,143 @@ class Postprocessor:
             out.append(Postprocessor._finish(config, pos32[a:b], prob[a:b], label[a:b], score[a:b], keep[a:b], corners[a:b],
                                              aligned))
         return out
+
+
+# ---------------------------------------------------------------------------------------------------- evaluation half
+def _cuda(a, name: str, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    t = torch.as_tensor(a)
+    if dtype is not None and t.dtype != dtype:
+        t = t.to(dtype)
+    if not t.is_cuda:
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{name}: the post-processor kernels need a GPU (no CPU fallback)")
+        t = t.cuda()
+    return t.contiguous()
+
+
+def _concat(frames, name: str, dtype: Optional[torch.dtype] = torch.float32) -> torch.Tensor:
+    """One CUDA tensor of a list of per-frame arrays / tensors (rows concatenated)."""
+    parts = [_cuda(f, name, dtype) for f in frames]
+    return torch.cat(parts, dim=0) if len(parts) > 1 else parts[0]
+
+
+def _nearest_in_frames(pos: torch.Tensor, ptr: List[int]) -> torch.Tensor:
+    """int32 [N]: every point's nearest other point of its frame (kneighbors_graph(pos, 1), postprocessing.py:463-467).
+    A frame of one point raises sklearn's error; empty frames are skipped, as the reference skips them."""
+    sizes = [b - a for a, b in zip(ptr[:-1], ptr[1:])]
+    if any(n == 1 for n in sizes):
+        raise ValueError("Expected n_neighbors < n_samples_fit, but n_neighbors = 1, n_samples_fit = 1")   # sklearn's error
+    if ptr[-1] == 0:
+        return torch.empty(0, dtype=torch.int32, device=pos.device)
+    bounds = [ptr[0]] + [b for a, b in zip(ptr[:-1], ptr[1:]) if b > a]
+    nn, _, _ = ops.knn_graph(pos.to(torch.float64), torch.tensor(bounds, dtype=torch.int64, device=pos.device), 1,
+                             want_edge_index=False)
+    return nn.view(-1)
+
+
+def _offsets(keep: torch.Tensor, ptr: torch.Tensor) -> torch.Tensor:
+    """int64 [B + 1]: offsets of the kept rows of each segment (segments given by ptr, int64 on the device)."""
+    csum = torch.cat((torch.zeros(1, dtype=torch.int64, device=keep.device), torch.cumsum(keep, 0, dtype=torch.int64)))
+    return csum.index_select(0, ptr)
+
+
+def _labels_column(class_labels) -> torch.Tensor:
+    t = torch.as_tensor(class_labels)
+    if t.dim() == 2 and t.shape[1] == 1:
+        t = t.view(-1)
+    if t.dim() != 1:
+        raise ValueError("class labels must be [N] or [N, 1]")
+    return _cuda(t, "class_labels", None)
+
+
+def _ground_truth(labels: torch.Tensor, boxes: torch.Tensor, pos: torch.Tensor, ptr: List[int], bb_invariance: str,
+                  bg_index: int, nn_index: Optional[torch.Tensor] = None, dedup: bool = True):
+    """Ground truth of a batch of frames: ONE decode launch and (dedup) ONE duplicate-removal launch over all frames.
+    -> (corners f64 [M, 4, 2], labels [M] in the input dtype, box offsets of the frames int64 [B + 1] on the device)."""
+    if bb_invariance not in INVARIANCE_CODES:
+        raise ValueError(f"unknown bb_invariance {bb_invariance!r}")
+    n = pos.shape[0]
+    if boxes.dim() != 2 or boxes.shape[0] != n or boxes.shape[1] not in (4, 5) or pos.shape != (n, 2) or labels.shape != (n,):
+        raise ValueError("shapes: class labels [N], boxes [N, 4|5], pos [N, 2]")
+    inv = INVARIANCE_CODES[bb_invariance]
+    if inv == 2 and nn_index is None:
+        nn_index = _nearest_in_frames(pos, ptr)            # (called for aligned boxes too: the reference searches them)
+    if inv != 2 or boxes.shape[1] == 4:
+        nn_index = None
+    keep, corners = ops.decode_ground_truth(labels.to(torch.float32), boxes, pos, nn_index, bg_index, inv)
+    ptr_dev = torch.tensor(ptr, dtype=torch.int64, device=pos.device)
+    idx = torch.nonzero(keep, as_tuple=False).view(-1)
+    corners, labels, box_ptr = corners.index_select(0, idx), labels.index_select(0, idx), _offsets(keep, ptr_dev)
+    if dedup:
+        keep = ops.remove_duplicate_boxes(corners, box_ptr)
+        idx = torch.nonzero(keep, as_tuple=False).view(-1)
+        corners, labels, box_ptr = corners.index_select(0, idx), labels.index_select(0, idx), _offsets(keep, box_ptr)
+    return corners, labels, box_ptr
+
+
+class GroundTruthExtractor:
+    """postprocessor/postprocessing.py:438-575, same method names and result shapes; tensors in HBM."""
+
+    @staticmethod
+    def get_absolute_object_bounding_boxes(class_labels, bounding_boxes, pos, bb_invariance: str, bg_index: int
+                                           ) -> Tuple[BoundingBoxes, torch.Tensor]:
+        """-> (absolute boxes of the nodes whose label != bg_index, in node order; their labels [M, 1] in the input dtype).
+        The angle is never adapted, and there is no score filter."""
+        labels = _labels_column(class_labels)
+        p, bb = _f32_cuda(pos, "pos"), _f32_cuda(bounding_boxes, "bounding_boxes")
+        corners, labels, _ = _ground_truth(labels, bb, p, [0, p.shape[0]], bb_invariance, bg_index, dedup=False)
+        return BoundingBoxes(corners, bb.shape[1] == 4), labels.view(-1, 1)
+
+    @staticmethod
+    def remove_duplicate_boxes(bounding_boxes, box_labels) -> Tuple[BoundingBoxes, torch.Tensor]:
+        """Drops box j when an earlier box of the graph has the same corners or corners within an L1 distance < 0.1
+        (postprocessing.py:552-575).  ``bounding_boxes``: ``BoundingBoxes`` or a list of ``BoundingBox``."""
+        if isinstance(bounding_boxes, BoundingBoxes):
+            corners, aligned = bounding_boxes.corners, bounding_boxes.is_aligned
+        else:
+            boxes = list(bounding_boxes)
+            aligned = boxes[0].is_aligned if boxes else True
+            corners = _cuda(np.array([np.asarray(b.corners, dtype=np.float64) for b in boxes]).reshape(-1, 4, 2), "corners",
+                            torch.float64)
+        corners = _cuda(corners, "corners", torch.float64)
+        labels = _cuda(box_labels, "box_labels", None).reshape(-1)
+        if labels.shape[0] != corners.shape[0]:
+            raise ValueError("one label per box")
+        keep = ops.remove_duplicate_boxes(corners, torch.tensor([0, corners.shape[0]], dtype=torch.int64, device=corners.device))
+        idx = torch.nonzero(keep, as_tuple=False).view(-1)
+        return BoundingBoxes(corners.index_select(0, idx), aligned), labels.index_select(0, idx).view(-1, 1)
+
+
+def _boxes_f32(boxes, width: int, name: str) -> torch.Tensor:
+    t = _f32_cuda(boxes, name)
+    if t.numel() == 0:
+        t = t.reshape(0, width)
+    if t.dim() != 2 or t.shape[1] != width:
+        raise ValueError(f"{name} must be [M, {width}]")
+    return t
+
+
+def point_iou_batched(boxes_pred: List, boxes_gt: List, points: List, box_aligned: bool) -> List[torch.Tensor]:
+    """``point_iou`` for a list of graphs in ONE set of launches: boxes_pred[f] [P_f, 4|5], boxes_gt[f] [G_f, 4|5] and
+    points[f] [N_f, 2] -> list of float64 [P_f, G_f] matrices (views into one packed tensor in HBM)."""
+    if not (len(boxes_pred) == len(boxes_gt) == len(points)):
+        raise ValueError("one entry per graph in boxes_pred, boxes_gt and points")
+    if len(points) == 0:
+        return []
+    width = 4 if box_aligned else 5
+    bp = [_boxes_f32(b, width, "boxes_pred") for b in boxes_pred]
+    bg = [_boxes_f32(b, width, "boxes_gt") for b in boxes_gt]
+    pts = [_f32_cuda(p, "points").reshape(-1, 2) for p in points]
+    ptrs = [[0], [0], [0]]
+    for lst, parts in zip(ptrs, (bp, bg, pts)):
+        for t in parts:
+            lst.append(lst[-1] + t.shape[0])
+    iou, out = ops.point_iou(torch.cat(bp), ptrs[0], torch.cat(bg), ptrs[1], torch.cat(pts), ptrs[2], not box_aligned)
+    return [iou[out[f]:out[f + 1]].view(bp[f].shape[0], bg[f].shape[0]) for f in range(len(points))]
+
+
+def point_iou(boxes_pred, boxes_gt, points, box_aligned: bool) -> torch.Tensor:
+    """utils/math.py:176-211: float64 [P, G] point IoU of every (predicted, ground-truth) box pair of one graph.  Boxes
+    float32 [x_min, y_min, x_max, y_max] (aligned) or [x, y, l, w, theta in degrees] (rotated); points: the graph's
+    coordinates [N, 2] (float32)."""
+    return point_iou_batched([boxes_pred], [boxes_gt], [points], box_aligned)[0]
