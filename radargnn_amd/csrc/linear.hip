@@ -20,19 +20,6 @@
 //               HBM once into that XCD's L2.
 #include "linear_common.h"
 
-#ifndef RGNN_NBUF
-#define RGNN_NBUF 2
-#endif
-#ifndef RGNN_MINW
-#define RGNN_MINW 2
-#endif
-#ifndef RGNN_STAGGER
-#define RGNN_STAGGER 0
-#endif
-#ifndef RGNN_WAVES8
-#define RGNN_WAVES8 0
-#endif
-
 namespace {
 
 
@@ -780,13 +767,14 @@ void launch_x3(LinParams p, hipStream_t s) {
   hipLaunchKernelGGL((k_linear_x3<BMT, BN, WGM, WGN, TM, TN, BKX, NSETS, IDX>), dim3((unsigned)grid), dim3(WGM * WGN * 64), lds, s, p);
 }
 
-constexpr int NBUF_DEFAULT = RGNN_NBUF;
+constexpr int NBUF_DEFAULT = 2;      // LDS stages of k_linear
+constexpr int WG_PER_CU_MAX = 2;     // work-groups per CU that the persistent grid of k_linear counts on, at most
 
 template <int BN, int WGM, int WGN, int TM, int TN, int NBUF = NBUF_DEFAULT, bool BUFL_ONLY = false>
 void launch(const LinParams& p, bool vec, bool bufl, hipStream_t s) {
   const size_t lds = (size_t)NBUF * (BM + BN) * LDK * sizeof(float);
   // persistent grid: enough workgroups to fill 256 CUs at the occupancy the LDS / register budget admits
-  int per_cu = (int)(160 * 1024 / lds) < RGNN_MINW ? (int)(160 * 1024 / lds) : RGNN_MINW;
+  int per_cu = (int)(160 * 1024 / lds) < WG_PER_CU_MAX ? (int)(160 * 1024 / lds) : WG_PER_CU_MAX;
   const int64_t tiles = (int64_t)p.mt * p.nt;
   int64_t grid = 256 * per_cu;
   if (grid > tiles) grid = tiles;
@@ -1159,11 +1147,7 @@ extern "C" int rgnn_linear_fwd(const rgnn_linear_args* a, rgnn_stream_t stream) 
     }
   } else if (a->n > 64) {
     p.nt = (a->n + 127) / 128;
-#if RGNN_WAVES8
-    launch<128, 4, 2, 1, 2>(p, vec, bufl, s);   // 8 waves of 32x64
-#else
     launch<128, 2, 2, 2, 2>(p, vec, bufl, s);   // 4 waves of 64x64
-#endif
   } else if (a->n > 32) {
     p.nt = 1;
     launch<64, 2, 2, 2, 1>(p, vec, bufl, s);

@@ -7,11 +7,9 @@
 #include <type_traits>
 #include <stdlib.h>
 
-#ifndef RGNN_EPI_AUX
-#define RGNN_EPI_AUX 0     // cache policy of the epilogue's stores (2 = nt, streaming)
-#endif
-
 namespace {
+
+constexpr int EPI_AUX = 0;   // cache policy of the epilogue's stores (2 = nt, streaming)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -115,17 +113,10 @@ __device__ __forceinline__ float direct_epilogue(const LinParams& p, f32x16 (&ac
   const bool full = m0 + BMT <= M;         // (ROWS: the table masks the rows beyond M of the last panel)
   float* stat_lds = stage;                 // [WGM][BN][STAT_LDS_ROWS] + [WGM] counts (stats.h)
   if constexpr (ROWS) {
-#ifdef RGNN_EPI_ABL_NO_INDEX     // (experiment: no index loads -- wrong rows)
-    for (int r = t; r < BMT; r += THREADS) row_tab[r] = (m0 + r < M) ? (int)(m0 + r) * ldo4 : OOB;
-#else
     for (int r = t; r < BMT; r += THREADS) {           // (an entry of -1 is an absent row: padding of a segmented list)
-      int ri = (m0 + r < M) ? p.row_index[m0 + r] : -1;
-#ifdef RGNN_EPI_ABL_SMALLOUT     // (experiment: every store lands in the first 4 096 output rows -- cache-resident, no HBM write traffic; wrong results)
-      if (ri >= 0) ri &= 4095;
-#endif
+      const int ri = (m0 + r < M) ? p.row_index[m0 + r] : -1;
       row_tab[r] = (ri >= 0) ? ri * ldo4 : OOB;
     }
-#endif
     __syncthreads();
   }
   auto run = [&](auto relu_c, auto stats_c) {
@@ -181,11 +172,11 @@ __device__ __forceinline__ float direct_epilogue(const LinParams& p, f32x16 (&ac
           if constexpr (ROWS) {
             const int rof = row_tab[(wm_u * TM + i) * 32 + rr + 4 * (lane >> 5)];
             const bool okr = rof != OOB;
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v), ro, (rof | (vo & OOB)) + (vo & 0x7fffffff), 0, RGNN_EPI_AUX);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v), ro, (rof | (vo & OOB)) + (vo & 0x7fffffff), 0, EPI_AUX);
             if (STATS) { if (i == 0 && r == 0) piv = v; const float d = v - piv; s1 += okr ? d : 0.f; s2 += okr ? d * d : 0.f; }
           } else {
             const bool okr = !MASK || ((int64_t)rowb + rr + 4 * (lane >> 5) < M);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v), ro, okr ? vo : OOB, so, RGNN_EPI_AUX);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v), ro, okr ? vo : OOB, so, EPI_AUX);
             so += ((r & 3) == 3) ? 5 * ldo4 : ldo4;  // one running SGPR instead of 16 precomputed row offsets
             if (STATS) { if (i == 0 && r == 0) piv = v; const float d = v - piv; s1 += okr ? d : 0.f; s2 += okr ? d * d : 0.f; }
           }

@@ -1,14 +1,19 @@
-// Dense layer  out = act([A1|A2] * W^T + bias)  on the bf16 matrix pipe (six-term split product, see linear.hip), with the
-// operands staged by LDS-DMA.  Replaces ATen addmm behind torch_geometric's dense Linear (gnn/gnn_models.py:137-178,
-// gnn/mpnn_layers.py:64-74,89-90) for the wide layers of the model (n > 64, K a multiple of 16).
+// Dense layer  out = act([A1|A2] * W^T + bias)  on the 16-bit matrix pipe (split product: three bf16 terms per operand and six
+// MFMAs per 16 k, see linear.hip, or two f16 terms and three MFMAs, see FMT below), with the operands staged by LDS-DMA.
+// Replaces ATen addmm behind torch_geometric's dense Linear (gnn/gnn_models.py:137-178, gnn/mpnn_layers.py:64-74,89-90) for the
+// wide layers of the model (n > 64, K a multiple of 16).  The three points below are written for the bf16x3 form.
 //
 // Why a second kernel.  The register-staged kernel (k_linear_x3) requests a k-step's operands into VGPRs, splits them and
 // writes them to LDS; its ISA shows that hipcc re-uses the fragment registers as load destinations and sinks the loads
 // behind most of the step's MFMAs, so every k-step opens with `s_waitcnt vmcnt(0)` on loads issued a few hundred cycles
 // earlier -- the HBM latency is paid once per step (r01: 0.31 of the bf16 peak, 37 % matrix-pipe busy).  Here
 //   * every operand byte travels HBM/L2 -> LDS with `buffer_load_dwordx4 ... lds` (no VGPRs, no ds_write), issued from
-//     inline asm so that hipcc neither counts nor drains them, two (weights) and three (activations) k-steps ahead of the
-//     MFMAs that use them, into rings of three / four LDS stages; one counted `s_waitcnt vmcnt(N)` + one barrier per step;
+//     inline asm so that hipcc neither counts nor drains them, ahead of the MFMAs that use them; one counted
+//     `s_waitcnt vmcnt(N)` + one barrier per step.  Two schedules exist (dma_ks below picks one per instantiation):
+//       SINGLE STEPS (bf16x3 form, four-wave work-groups): a step is 16 k; weights two steps ahead into a ring of three LDS
+//         stages, activations three ahead into a ring of four;
+//       DOUBLE STEPS (f16x2 form with eight waves): a step is two 16-k sub-stages; weights one step ahead (ring of two),
+//         activations two ahead (ring of three; two for column tiles wider than 160);
 //   * the activation tile lies in LDS as raw fp32 and is split into its three bf16 terms AFTER the fragment read, by the
 //     one wave that owns those rows: the eight waves of a work-group are stacked along M (32 rows x BN columns each), so
 //     no activation element is split twice and the 32 x 16 fp32 fragment of a wave is two ds_read_b128 per lane.  A wave
@@ -16,56 +21,18 @@
 //     during the MFMAs of step g;
 //   * the weight planes (pre-split, [k/16][3][n][16] bf16) are shared by all eight waves: 3 x TN ds_read_b128 per wave and
 //     k-step feed 6 x TN MFMAs.
-// The accumulation order of every output element (k-steps of 16 ascending; per step l h', h l', m m', m h', h m', h h') is the
-// same as in k_linear_x3, so the two kernels agree bit for bit (tests/test_gpu_gnn.py).
+// The accumulation order of every output element (16-k blocks ascending; per block l h', h l', m m', m h', h m', h h' -- f16x2:
+// l h', h l', h h') is the same as in k_linear_x3 under either schedule, so the two kernels agree bit for bit
+// (tests/test_gpu_gnn.py).
 //
-// LDS stage (k-step of 16):  A: [256 rows][64 B]   chunk c (4 floats) of row r at 16-byte position c ^ ((r >> 2) & 3)
+// LDS stage of 16 k (a double step's stage is two of them back to back; the f16x2 form has two weight planes):
+//                            A: [256 rows][64 B]   chunk c (4 floats) of row r at 16-byte position c ^ ((r >> 2) & 3)
 //                            W: [3][BN rows][32 B] chunk c (8 bf16)  of row r at position          c ^ ((r >> 3) & 1)
 // -- ds_read_b128 serves the lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31} (+32) one at a time; with these swizzles the
 // 16 rows of a group fall on 16 distinct slots of the 256-byte bank row (SQ_LDS_BANK_CONFLICT = 0).  LDS-DMA writes
 // M0 + 16 * lane, so the swizzle is applied to the per-lane SOURCE address (the 4 / 2 lanes of a row still cover one
 // contiguous 64 / 32-byte run of global memory).
 #include "linear_common.h"
-
-#ifndef RGNN_DMA_SPREAD
-#define RGNN_DMA_SPREAD 1   // issue the DMA pieces of a step between its MFMA groups instead of back to back behind the barrier
-#endif
-#ifndef RGNN_DMA_SK_MAX_FILL
-#define RGNN_DMA_SK_MAX_FILL 88   // stream-K only when the static schedule's tile rounds would be less than 88 % full
-#endif
-#ifndef RGNN_DMA_PIN
-#define RGNN_DMA_PIN 1
-#endif
-#ifndef RGNN_DMA_TRACK
-#define RGNN_DMA_TRACK 1    // the epilogue keeps max |out| per lane (one v_max per element; the atomic only when out_absmax is given)
-#endif
-#ifndef RGNN_DMA_POST_EPI_WAIT
-#define RGNN_DMA_POST_EPI_WAIT 0
-#endif
-#ifndef RGNN_DMA_PP
-#define RGNN_DMA_PP 0       // ping-pong (see the k-loop): 1 = waves 4-7 run half a k-step behind waves 0-3; 2 = ... and at s_setprio 1
-#endif
-#ifndef RGNN_DMA_KS
-#define RGNN_DMA_KS 2       // 16-k sub-stages per k-step (one counted wait + one barrier + one request round per step) where the LDS allows it: see dma_ks
-#endif
-#ifndef RGNN_DMA_KS_MAX_TN
-#define RGNN_DMA_KS_MAX_TN 8
-#endif
-#ifndef RGNN_DMA_ABL
-#define RGNN_DMA_ABL 0      // experiments only: 1 no epilogue, 4 no MFMAs, 8 no DMA, 16 no activation split, 32 no barrier, 64 no DMA wait, 128 no weight-fragment LDS reads, 256 no weight DMA pieces, 512 no activation DMA pieces (results are wrong by construction)
-#endif
-
-#ifndef RGNN_DMA_TIMING
-#define RGNN_DMA_TIMING 0   // experiments only (tools/x3_bench): per-wave s_memtime sums of the k-step's parts, read back through rgnn_debug_dma_timing
-#endif
-#if RGNN_DMA_TIMING
-__device__ unsigned long long g_dma_t[2048 * 8];
-extern "C" int rgnn_debug_dma_timing(unsigned long long* host, int clear) {
-  if (clear) { static unsigned long long z[2048 * 8]; return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_dma_t), z, sizeof(z)); }
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_dma_t), sizeof(g_dma_t));
-}
-#define TSTAMP() ({ __builtin_amdgcn_sched_barrier(0); unsigned long long _t = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); _t; })
-#endif
 
 namespace {
 
@@ -103,16 +70,15 @@ __device__ __forceinline__ i32x4 make_rsrc(const void* base, int bytes) {
 
 constexpr int DMA_BM_MAX = 256;  // rows per work-group tile: 8 waves x 32 (4-wave work-groups: 128)
 constexpr int DMA_BK = 16;       // k per step = one MFMA k-extent
-// Prefetch depth DW: weights are requested DW k-steps ahead of the MFMAs that use them (ring of DW + 1 stages), activations
-// DW + 1 ahead (ring of DW + 2: they are split one step ahead); the counted wait of a step lets DW - 1 groups of requests stay
-// outstanding.  DW = 2.  DW = 3 (RGNN_DMA_DEPTH=3: f16x2 form, TN <= 7, +30 KB of LDS; NOT with a1_scale_shift at TN = 7, where
-// the table no longer fits) was built to test whether the k-loop's operand rate is (bytes in flight) / latency: bit-identical
-// and no faster (profiles/r03_x3_bench_dma_depth.txt) -- it is not.
-#ifndef RGNN_DMA_DEPTH
-#define RGNN_DMA_DEPTH 2
-#endif
-// DOUBLE STEPS (r06, dma_ks = 2: f16x2 form, eight waves, column tiles of up to 160).  A k-step is TWO 16-k sub-stages behind ONE
-// counted wait, ONE barrier and ONE round of request bookkeeping: the s_memtime build (profiles/r06_dense_kloop_probes.txt) put 181
+// SINGLE STEPS: prefetch depth DW = DMA_DEPTH.  Weights are requested DW k-steps ahead of the MFMAs that use them (ring of DW + 1
+// stages), activations DW + 1 ahead (ring of DW + 2: they are split one step ahead); the counted wait of a step lets DW - 1 groups
+// of requests stay outstanding.  (A depth of 3 was bit-identical and no faster: profiles/r03_x3_bench_dma_depth.txt.)
+constexpr int DMA_DEPTH = 2;
+constexpr int DMA_KS = 2;            // 16-k sub-stages per k-step where the LDS allows it (double steps, below) ...
+constexpr int DMA_KS_MAX_TN = 8;     // ... up to this column-tile width
+constexpr int DMA_SK_MAX_FILL = 88;  // stream-K only when the static schedule's tile rounds would be less than 88 % full
+// DOUBLE STEPS (r06, dma_ks = 2: f16x2 form, eight waves).  A k-step is TWO 16-k sub-stages behind ONE counted wait, ONE barrier
+// and ONE round of request bookkeeping: a cycle-counter build of the k-loop (profiles/r06_dense_kloop_probes.txt) put 181
 // + 591 cycles of a 2 660-cycle step into the wait and the barrier, and the scalar bookkeeping of a request round into the 679
 // cycles of its load half, against 480 cycles of MFMA issue per wave.  The sub-stages keep their layout (a stage is two of them
 // back to back), every accumulator still sees its 16-k products in ascending order (bit-identical results), and the fragment of
@@ -120,7 +86,7 @@ constexpr int DMA_BK = 16;       // k per step = one MFMA k-extent
 // weights one double step ahead (ring of two), activations THREE double stages for a lead of two steps: the slot of A(g) is
 // free once its second half has been read in the first half of step g, and A(g + 3) is requested into it in the second half.
 __host__ __device__ constexpr int dma_ks(int tn, int npl, int wv) {
-  return (RGNN_DMA_KS == 2 && !RGNN_DMA_TIMING && !RGNN_DMA_PP && npl == 2 && wv == 8 && tn <= RGNN_DMA_KS_MAX_TN) ? 2 : 1;
+  return (npl == 2 && wv == 8 && tn <= DMA_KS_MAX_TN) ? DMA_KS : 1;
 }
 // ... column tiles wider than 160 have no room for three double stages of activations (224 columns: 96 + 56 KB of rings + 21.5 KB
 // of statistics exchange): TWO stages there.  A(g + 2) is still requested in the second half of step g, into the slot whose second
@@ -129,20 +95,19 @@ __host__ __device__ constexpr int dma_ks(int tn, int npl, int wv) {
 // step, the weights' own.
 __host__ __device__ constexpr int dma_a_ring(int tn, int npl, int wv) { return dma_ks(tn, npl, wv) == 2 ? (tn <= 5 ? 3 : 2) : 0; }
 __host__ __device__ constexpr int dma_depth(int tn, int npl, int wv = 8) {
-  return dma_ks(tn, npl, wv) == 2 ? 1 : (RGNN_DMA_DEPTH >= 3 && npl == 2 && tn <= 7) ? 3 : 2;
+  return dma_ks(tn, npl, wv) == 2 ? 1 : DMA_DEPTH;
 }
 // (wv = waves per work-group: 8 -- one work-group of 256 rows per CU -- or 4: two work-groups of 128 rows per CU, which drift
 //  apart so that one of them loads and multiplies while the other stores its tile; see launch_dma)
 __host__ __device__ constexpr int dma_w_pieces(int bn, int npl = 3, int wv = 8) { return (npl * bn * 2 + 64 * wv - 1) / (64 * wv); }   // 16-B chunks / threads
 __host__ __device__ constexpr int dma_w_stage(int bn, int npl = 3, int wv = 8) { return dma_w_pieces(bn, npl, wv) * 64 * wv * 16; }
-__host__ __device__ constexpr bool dma_pp(int wv, int npl) { return RGNN_DMA_PP != 0 && wv == 8 && npl == 2; }   // ping-pong schedule (k-loop): f16x2 form, 8 waves
 __host__ __device__ constexpr int dma_lds_bytes(int bn, int npl = 3, int wv = 8) {
   const int ks = dma_ks(bn / 32, npl, wv), dw = dma_depth(bn / 32, npl, wv);
   // (double steps: the weight stage is packed -- both sub-stages' chunks back to back, no padding to whole pieces: a wave whose
   //  part of the last piece lies beyond the stage does not issue it)
   const int w_stage = ks == 2 ? ks * npl * bn * 2 * 16 : dma_w_stage(bn, npl, wv);
   const int a_ring = ks == 2 ? dma_a_ring(bn / 32, npl, wv) : dw + 2;
-  return a_ring * ks * (32 * wv * DMA_BK * 4) + (dw + 1 + (dma_pp(wv, npl) ? 1 : 0)) * w_stage +
+  return a_ring * ks * (32 * wv * DMA_BK * 4) + (dw + 1) * w_stage +
          stat_lds_floats(wv, bn) * 4 + 32 * wv * 4;
 }
 
@@ -179,10 +144,9 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
   constexpr int W_SUB = KS == 2 ? NWQ * 16 : dma_w_stage(BN, NPL, WV);   // one sub-stage of weight planes
   constexpr int W_STAGE = KS * W_SUB;
   constexpr int DW = dma_depth(TN, NPL, WV);       // prefetch depth of the weight stream (activations: DW + 1; double steps: DW + 2)
-  constexpr bool PP = dma_pp(WV, NPL);                  // ping-pong schedule of the two waves of a SIMD (k-loop)
-  constexpr int DMA_A_RING = KS == 2 ? dma_a_ring(TN, NPL, WV) : DW + 2, DMA_W_RING = DW + 1 + (PP ? 1 : 0);
+  constexpr int DMA_A_RING = KS == 2 ? dma_a_ring(TN, NPL, WV) : DW + 2, DMA_W_RING = DW + 1;
   constexpr bool AR2 = KS == 2 && DMA_A_RING == 2;   // two activation stages: A(g + 1) is awaited in the middle of step g
-  static_assert(KS == 1 || (DW == 1 && !PP), "double steps: weights one step ahead, activations two");
+  static_assert(KS == 1 || DW == 1, "double steps: weights one step ahead, activations two");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   char* const lds = (char*)smem;
   char* const lds_w = lds + DMA_A_RING * DMA_A_STAGE;
@@ -224,7 +188,7 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
   //     ranges to TEAMS of nt work-groups that walk the same panels in step was built too and measured 166 us (bit-identical).
   const int sk_rounds = (n_items + g8 - 1) / g8;
   const bool sk = p.sk_ws != nullptr && p.nt == 1 && n_items >= g8 && nk >= 8 &&
-                  n_items * 100 < sk_rounds * g8 * RGNN_DMA_SK_MAX_FILL &&
+                  n_items * 100 < sk_rounds * g8 * DMA_SK_MAX_FILL &&
                   (float)n_items / (float)g8 + 2.f * BN / (float)(K + BN) + 0.25f < (float)sk_rounds;
   //   parallel split-K (few items: one frame is 12 row panels, the XCD's work-groups would mostly idle and the layer's
   //     latency is one work-group's whole k-loop): every item is cut into S k-ranges done by S work-groups at the same time,
@@ -296,7 +260,8 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
   const i32x4 ra2_d = make_rsrc(p.A2 ? p.A2 : p.A1, p.A2 ? p.ext_a2 : 0);
   const i32x4 rw_d = make_rsrc(p.Wp, p.ext_wp);
 
-  // ---- two load streams walk the (tile, k-step) sequence of the MFMAs: weights two steps ahead, activations three.
+  // ---- two load streams walk the (tile, k-step) sequence of the MFMAs: weights two steps ahead, activations three (double steps:
+  // one and two).
   // Activations: a wave requests ITS OWN 32 rows (piece s: rows 32 wave + 16 s + (lane >> 2), LDS position lane & 3 holds
   // logical chunk (lane & 3) ^ ((row >> 2) & 3)), so nobody else ever touches them: no barrier between the DMA and the
   // fragment read, only the wave's own vmcnt.  Weights: piece s covers LDS chunks 512 s + t of the stage, all waves read all.
@@ -309,8 +274,7 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
       const int r = 16 * s + (lane >> 2);
       const int64_t gm = m0 + r;
       int64_t row = -1;
-      if (gm < M) row = (IDX && !(RGNN_DMA_ABL & 1024)) ? (int64_t)p.row_index[gm] : gm;   // (1024: experiment, no index loads)
-      if ((RGNN_DMA_ABL & 2048) && row >= 0) row &= 1023;                                 // (2048: experiment, activations from cache-resident rows)
+      if (gm < M) row = IDX ? (int64_t)p.row_index[gm] : gm;
       const int c = ((lane & 3) ^ ((r >> 2) & 3)) * 16;
       va1[s] = (row >= 0) ? (int)(row * p.lda1 * 4) + c : OOB;
       va2[s] = (row >= 0) ? (int)(row * p.lda2 * 4) + c : OOB;
@@ -353,9 +317,6 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
     rq.w_base = __builtin_amdgcn_readfirstlane(lds0 + DMA_A_RING * DMA_A_STAGE + w_ring * W_STAGE + wave * 1024);
   };
   auto req_piece = [&](int i) {                     // i is a compile-time constant at every call site
-    if (RGNN_DMA_ABL & 8) return;
-    if ((RGNN_DMA_ABL & 256) && i < NW) return;       // experiment: no weight pieces
-    if ((RGNN_DMA_ABL & 512) && i >= NW) return;      // experiment: no activation pieces
     if (i < NW) {
       if (i < NW_ALL || i * DMA_THREADS + wave * 64 < KS * NWQ)    // (wave-uniform: the last piece of a packed double stage)
         dma16(rw_d, vw[i] | rq.w_kill, rq.w_soff, rq.w_base + i * (DMA_THREADS * 16));
@@ -561,10 +522,6 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
     }
   };
   float amax = 0.f;                                 // |out| seen by this lane (out_absmax)
-#ifndef RGNN_DMA_PRIO_YOUNG
-#define RGNN_DMA_PRIO_YOUNG 0
-#endif
-  if (((PP && RGNN_DMA_PP == 2) || RGNN_DMA_PRIO_YOUNG) && WV == 8 && (wave >> 2) == 1) __builtin_amdgcn_s_setprio(1);   // (static priority for the younger half: MI355X_MICROARCH.md item 4)
   Cursor cc = cursor_begin();                       // compute stream
   int ca_ring = 0, cw_ring = 0, ca_cur = 0;         // ... and the ring slots it reads next (ca_cur: double steps, the slot of the CURRENT step's activations)
   a_offsets(w_base);
@@ -579,7 +536,7 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
     dma_wait<NW_ALL + (AR2 ? 1 : 2) * KS * NA>();   // A(0) is in (waves that issue the partial last weight piece: that one too)
   } else {
 #pragma unroll
-    for (int d = 0; d < DW; d++) { issue_w(); issue_a(); }   // W(0), A(1); W(1), A(2); (W(2), A(3))
+    for (int d = 0; d < DW; d++) { issue_w(); issue_a(); }   // W(0), A(1); W(1), A(2)
     dma_wait<DW * NLD>();                   // A(0) is in
   }
   Planes cur = read_a(0, cc.kt);
@@ -597,7 +554,7 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
     for (int j = 0; j < TN; j++) {
       const int gn = ct * BN + j * 32 + (lane & 31);
       float b = 0.f;
-      if (gn < p.n && !(RGNN_DMA_ABL & 1024)) {
+      if (gn < p.n) {
         const float* bp = (gn < p.w_split) ? p.bias1 : p.bias2;
         if (bp) b = bp[(gn < p.w_split) ? gn : gn - p.w_split];
       }
@@ -605,72 +562,35 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
     }
   };
   load_bias(w_base % p.nt);
-  int fresh = 0;                                    // k-steps left whose operands were requested before the last epilogue's stores
-#if RGNN_DMA_TIMING
-  unsigned long long tm_wait = 0, tm_bar = 0, tm_p1 = 0, tm_p2 = 0, tm_epi = 0, tm_steps = 0, tm_drain = 0, tm_own = 0;
-  const unsigned long long tm_begin = TSTAMP();
-#endif
   for (;;) {                                        // items of this work-group
     // accumulators: zeros, or -- last item of a stream-K range whose lower k-steps another work-group did -- its hand-over
     if (!psk && cc.j == w_count - 1 && w_kb_last > 0) load_partial(); else zero_acc();
     const int item = cc.item;
     if (p.nt > 1) load_bias(item % p.nt);
     const bool head_only = cc.j == 0 && cc.kend < nk;   // the item's upper k-range belongs to the next work-group
-    // PING-PONG (r06).  A k-step of a wave is a LOAD half P1 (scalar bookkeeping, its two activation pieces, the fragment read and
-    // split of the next step, the first weight-fragment reads) and a MATRIX half P2 (the MFMAs with the remaining fragment reads and
-    // the weight pieces between them).  With one barrier per step the two waves of a SIMD (w and w + 4) run the same half at the
-    // same time: the matrix pipe idles through both P1s and is then asked for both P2s.  With a second barrier between the halves
-    // and waves 4-7 entering the item one barrier LATE (waves 0-3 leave it one barrier late), every barrier interval pairs one
-    // wave's P1 with its SIMD partner's P2 (MI355X_MICROARCH.md, "Two waves per SIMD": matrix beside memory is the pairing that
-    // nets).  The barrier protocol still holds: a wave waits for its own pieces of W(g) before ITS barrier B1(g), and both of
-    // anybody's P2(g) lie behind everybody's B1(g).  ALL pieces of a step go out in its load half -- an LDS-DMA piece costs the
-    // issuing wave ~110 cycles when eight waves issue at once (the CU accepts one per ~20 cycles), and in the matrix half those
-    // cycles stop the wave's MFMA issue: measured with s_memtime, 450 of a matrix half's 1 200 cycles -- so the weight ring
-    // has one stage more: waves 0-3 request W(g + 2) while waves 4-7 still multiply with W(g - 1); the slot they fill held W(g - 2).
-    // Activation stages are private to a wave.
-    if (PP && (wave >> 2) == 1) __builtin_amdgcn_s_barrier();
+    // (One barrier per k-step: the two waves of a SIMD run the same half of a step at the same time.  A ping-pong of the two, with
+    //  a second barrier per step, was built and not adopted: DESIGN.md section 4.1.)
     for (;;) {                                      // k-steps
-      // step g.  In flight: W(g), A(g+1) (requested during step g-2) and W(g+1), A(g+2) (step g-1).
-      // (RGNN_DMA_POST_EPI_WAIT: the first DW steps behind an epilogue need pieces requested BEFORE its 16 TN stores, and the
-      //  counter retires in order -- those stores may stay in flight, up to the counter's 63)
-#if RGNN_DMA_TIMING
-      const unsigned long long ts0 = TSTAMP();
-#endif
-      if (RGNN_DMA_POST_EPI_WAIT && fresh > 0) {
-        fresh--;
-        dma_wait<((DW - 1) * NLD + 16 * TN < 63) ? (DW - 1) * NLD + 16 * TN : 63>();
-      } else if (!(RGNN_DMA_ABL & 64)) dma_wait<KS == 2 ? KS * NA : (DW - 1) * NLD>();   // this wave's pieces of W(g) and its A(g+1) have landed (double steps: only A(g+2) may be outstanding)
-#if RGNN_DMA_TIMING
-      const unsigned long long ts1 = TSTAMP();
-#endif
-      if (!(RGNN_DMA_ABL & 32)) __builtin_amdgcn_s_barrier();   // ... and everybody's W(g); nobody still reads the weight stage refilled next
-#if RGNN_DMA_TIMING
-      const unsigned long long ts2 = TSTAMP();
-#endif
+      // step g (single steps; the double step's own ring walk is in its block below).  In flight: W(g), A(g+1) (requested during
+      // step g-2) and W(g+1), A(g+2) (step g-1).
+      dma_wait<KS == 2 ? KS * NA : (DW - 1) * NLD>();   // this wave's pieces of W(g) and its A(g+1) have landed (double steps: only A(g+2) may be outstanding)
+      __builtin_amdgcn_s_barrier();                     // ... and everybody's W(g); nobody still reads the weight stage refilled next
       req_begin();                                    // W(g+2), A(g+3) (its slot held A(g-1), split by this wave during step g-2)
-      if (PP || !RGNN_DMA_SPREAD) {                   // (ping-pong: every piece goes out in the load half)
-  #pragma unroll
-        for (int i = 0; i < NLD; i++) req_piece(i);
-      }
       // k-step of the NEXT compute step (the fragment split now): the next one of this item, or the first of the next item
       const int kt_nxt = (cc.kt + 1 < cc.kend) ? cc.kt + 1 : ((cc.j + 1 == w_count - 1) ? w_kb_last : 0);
       const int aslot_nxt = aff_seg ? (((cc.kt + 1 < cc.kend) ? cc.j : cc.j + 1) & 1) : 0;
-      // (ping-pong: only the two LDS reads belong to the load half; the split's ~30 VALU instructions ride between the MFMAs)
-      RawA raw_nxt;
       Planes nxt;
       if constexpr (KS == 1) {
-        raw_nxt = load_a(ca_ring);
-        if (!PP) nxt = (RGNN_DMA_ABL & 16) ? cur : split_a(raw_nxt, kt_nxt, aslot_nxt);   // split for the NEXT step: overlaps this step's MFMAs
+        nxt = split_a(load_a(ca_ring), kt_nxt, aslot_nxt);   // split for the NEXT step: overlaps this step's MFMAs
         ca_ring = (ca_ring == DMA_A_RING - 1) ? 0 : ca_ring + 1;
       }
       const char* st = lds_w + cw_ring * W_STAGE + b_off;
       cw_ring = (cw_ring == DMA_W_RING - 1) ? 0 : cw_ring + 1;
-      auto read_b = [&](int j, raw16x8 (&b)[NPL]) {
+      // (`cur` is captured and not read: a capture left behind by a removed experiment.  Without it hipcc numbers 28 registers of the
+      //  four-wave instances differently -- same instructions, same resources; it stays until a change that is measured takes it out)
+      auto read_b = [&st, &cur](int j, raw16x8 (&b)[NPL]) {
   #pragma unroll
-        for (int pl = 0; pl < NPL; pl++) {
-          if (RGNN_DMA_ABL & 128) { b[pl] = cur.h; continue; }       // experiment: no weight-fragment reads from LDS
-          b[pl] = *(const raw16x8*)(st + j * 32 * 32 + pl * W_PLANE);
-        }
+        for (int pl = 0; pl < NPL; pl++) b[pl] = *(const raw16x8*)(st + j * 32 * 32 + pl * W_PLANE);
       };
       // one MFMA product of two operand terms, fp32 accumulate (bf16 or f16 words according to FMT)
       auto mm = [&](const raw16x8& a, const raw16x8& b, const f32x16& c) -> f32x16 {
@@ -680,12 +600,6 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
           return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
       };
       auto mul = [&](f32x16& c, const Planes& a, const raw16x8 (&b)[NPL]) {   // smallest terms first: l h', h l', m m', m h', h m', h h'
-        if (RGNN_DMA_ABL & 4) {
-  #if defined(__HIP_DEVICE_COMPILE__)
-          asm volatile("" :: "v"(b[0]), "v"(b[1]), "v"(b[NPL - 1]), "v"(a.h), "v"(a.m), "v"(a.l));
-  #endif
-          return;
-        }
         if constexpr (FMT == 1) {
           c = mm(a.l, b[0], c);
           c = mm(a.h, b[1], c);
@@ -704,7 +618,6 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
       // between two MFMAs on the SAME accumulator -- that position costs ~43 cycles per instruction, any other ~6
       // (MI355X_MICROARCH.md, per-instruction constants).  Each accumulator still sees its k-steps and terms in the same order.
       auto mul2 = [&](f32x16& c0, f32x16& c1, const Planes& a, const raw16x8 (&b0)[NPL], const raw16x8 (&b1)[NPL]) {
-        if (RGNN_DMA_ABL & 4) { mul(c0, a, b0); mul(c1, a, b1); return; }
         if constexpr (FMT == 1) {
           c0 = mm(a.l, b0[0], c0); c1 = mm(a.l, b1[0], c1);
           c0 = mm(a.h, b0[1], c0); c1 = mm(a.h, b1[1], c1);
@@ -732,11 +645,11 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
         const char* const stw = st;
 #pragma unroll
         for (int h = 0; h < KS; h++) {
-          if (AR2 && h == 1 && !(RGNN_DMA_ABL & 64)) dma_wait<NW_ALL>();   // two stages: A(g + 1) has landed (behind it only W(g + 1))
+          if (AR2 && h == 1) dma_wait<NW_ALL>();   // two stages: A(g + 1) has landed (behind it only W(g + 1))
           const RawA raw = (h == 0) ? load_a(ca_cur, 1) : load_a(ca_ring, 0);
           const int ks_n = (h == 0) ? cc.kt * KS + 1 : kt_nxt * KS;
           const int asl = (h == 0) ? (aff_seg ? (cc.j & 1) : 0) : aslot_nxt;
-          nxt = (RGNN_DMA_ABL & 16) ? cur : split_a(raw, ks_n, asl);
+          nxt = split_a(raw, ks_n, asl);
           st = stw + h * W_SUB;
           read_unit(0, bq[0]);
           int piece = (h == 0) ? 0 : NW;                  // (compile-time after unrolling)
@@ -753,7 +666,7 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
             else mul(acc[0][2 * q], cur, bq[cb][0]);
           }
 #if defined(__HIP_DEVICE_COMPILE__)
-          if (RGNN_DMA_PIN) asm volatile("" :: "v"(nxt.h), "v"(nxt.l));
+          asm volatile("" :: "v"(nxt.h), "v"(nxt.l));
 #endif
           cur = nxt;
         }
@@ -763,91 +676,35 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
         if (cursor_next(cc)) break;
         continue;
       }
-      if (!PP) read_unit(0, bq[0]);
-      bool item_done = false;
-      if (PP) {                                         // ---- end of the load half
-#if RGNN_DMA_TIMING
-#if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("" :: "v"(raw_nxt.x0.x), "v"(raw_nxt.x0.w), "v"(raw_nxt.x1.x), "v"(raw_nxt.x1.w));
-#endif
-        tm_own += TSTAMP() - ts2;
-#endif
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        read_unit(0, bq[0]);                            // (W(g): waves 4-7 wait for their pieces of it only in front of THIS barrier)
-        nxt = (RGNN_DMA_ABL & 16) ? cur : split_a(raw_nxt, kt_nxt, aslot_nxt);
-        req_end();
-        item_done = cursor_next(cc);
-      }
-#if RGNN_DMA_TIMING
-      const unsigned long long ts3 = TSTAMP();
-#endif
+      read_unit(0, bq[0]);
       int piece = 0;                                    // (compile-time after unrolling)
   #pragma unroll
       for (int q = 0; q < NP; q++) {
         const int cb = q & 1, nb = cb ^ 1;
         if (q + 1 < NP) read_unit(q + 1, bq[nb]);
-        if (RGNN_DMA_SPREAD && !PP) {
   #pragma unroll
-          for (int u = 0; u < (NLD + NP - 1) / NP; u++)
-            if (piece < NLD) req_piece(piece++);
-        }
+        for (int u = 0; u < (NLD + NP - 1) / NP; u++)
+          if (piece < NLD) req_piece(piece++);
         if (2 * q + 1 < TN) mul2(acc[0][2 * q], acc[0][2 * q + 1], cur, bq[cb][0], bq[cb][1]);
         else mul(acc[0][2 * q], cur, bq[cb][0]);
       }
 #if defined(__HIP_DEVICE_COMPILE__)
       // (keeps the split of the next step's activation fragment inside the MFMA block: left alone, hipcc sinks its ~50 VALU
       // instructions into the loop latch, behind all MFMAs, where both waves of a SIMD run them with the matrix pipe idle)
-      if (RGNN_DMA_PIN) asm volatile("" :: "v"(nxt.h), "v"(nxt.m), "v"(nxt.l));
+      asm volatile("" :: "v"(nxt.h), "v"(nxt.m), "v"(nxt.l));
 #endif
-      if (!PP) req_end();
-#if RGNN_DMA_TIMING
-      {
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-        for (int j = 0; j < TN; j++) asm volatile("" : "+v"(acc[0][j]));
-#endif
-        const unsigned long long ts4 = TSTAMP();
-        tm_wait += ts1 - ts0; tm_bar += ts2 - ts1; tm_p1 += ts3 - ts2; tm_p2 += ts4 - ts3; tm_steps++;
-      }
-#endif
+      req_end();
       cur = nxt;
-      if (PP ? item_done : cursor_next(cc)) break;  // the item's (sub-)range is complete
+      if (cursor_next(cc)) break;                     // the item's (sub-)range is complete
     }
-    if (PP && (wave >> 2) == 0) __builtin_amdgcn_s_barrier();
-#if RGNN_DMA_TIMING
-    unsigned long long te0_keep = 0;
-#endif
     if (head_only) {
       store_partial();
     } else {
       if (psk) combine();
-      else fresh = DW;
       const int panel = xcd + 8 * (item / p.nt);
-#if RGNN_DMA_TIMING
-      te0_keep = TSTAMP();
-#endif
-      if (!(RGNN_DMA_ABL & 1))
-        amax = direct_epilogue<BN, WV, 1, 1, TN, DMA_BM, IDX, RGNN_DMA_TRACK != 0>(p, acc, (int64_t)panel * DMA_BM, (item % p.nt) * BN, panel, M,
-                                                                                  stat_lds, row_tab, bias_r, FMT == 1 ? out_mul : 1.f, amax);
-#if defined(__HIP_DEVICE_COMPILE__)
-      else {
-#pragma unroll
-        for (int j = 0; j < TN; j++) asm volatile("" :: "v"(acc[0][j]));
-      }
-#endif
+      amax = direct_epilogue<BN, WV, 1, 1, TN, DMA_BM, IDX, true>(p, acc, (int64_t)panel * DMA_BM, (item % p.nt) * BN, panel, M,
+                                                                  stat_lds, row_tab, bias_r, FMT == 1 ? out_mul : 1.f, amax);
     }
-#if RGNN_DMA_TIMING
-    if (!head_only) {
-      const unsigned long long te1 = TSTAMP();
-      tm_epi += te1 - te0_keep;
-      if (RGNN_DMA_TIMING == 2) {                          // (the drain of the stores -- and of the pieces prefetched for the next item)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        tm_drain += TSTAMP() - te1;
-      }
-    }
-#endif
     if (cc.j >= w_count) break;
     if (aff_seg) {                                  // item cc.j - 1 is finished: its table slot takes the item after the next one
       __syncthreads();
@@ -855,12 +712,6 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
       __syncthreads();
     }
   }
-#if RGNN_DMA_TIMING
-  if (lane == 0) {
-    unsigned long long* o = g_dma_t + ((blockIdx.x & 255) * 8 + (wave & 7)) * 8;
-    o[0] = tm_wait; o[1] = tm_bar; o[2] = tm_p1; o[3] = tm_p2; o[4] = tm_epi; o[5] = tm_steps; o[6] = TSTAMP() - tm_begin; o[7] = RGNN_DMA_PP ? tm_own : tm_drain;
-  }
-#endif
   dma_wait<0>();                                    // (killed pieces of the exhausted streams)
   if (p.out_absmax) {                               // one atomic per work-group, into the slot of this work-group
 #pragma unroll

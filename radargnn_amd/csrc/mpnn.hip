@@ -12,21 +12,6 @@
 #include "common.h"
 #include <stdlib.h>
 
-#ifndef RGNN_MPNN_NT_STORE
-#define RGNN_MPNN_NT_STORE 1   // the aggregated rows leave with streaming stores (they are not read again here; kept out of L2 they leave it to the rows of Q: -27 % HBM reads, -5 % time)
-#endif
-#ifndef RGNN_MPNN_SCALAR_EA
-#define RGNN_MPNN_SCALAR_EA 0  // k_mpnn_max: an edge's attribute row through the scalar cache (s_load_dwordx8, one edge ahead) instead of a 64-edge
-                               // block in VGPRs + 8 v_readlane per edge: 54 -> 46 VALU per edge, bit-identical, and SLOWER -- 203 -> 212 us on the C2
-                               // graph, 539 -> 631 us at k = 20 (tools/mpnn_bench.py, same call): the kernel is not bound by its VALU issue slots
-#endif
-#ifndef RGNN_MPNN_NT_LOAD
-#define RGNN_MPNN_NT_LOAD 0    // streaming loads for the edge stream (sources, attributes): -4 % in tools/mpnn_bench.py, nothing inside the step
-#endif
-#ifndef RGNN_MPNN_ABL
-#define RGNN_MPNN_ABL 0     // experiments only (wrong results): 1 cache-resident gathers, 2 one of the eight FMA terms, 4 no stores
-#endif
-
 namespace {
 
 constexpr int RGNN_MPNN_QUEUE_INTS = 8 * 8 * 16;  // ticket counters: up to 8 channel blocks x 8 XCDs, 64 B apart
@@ -199,11 +184,8 @@ __global__ __launch_bounds__(MP_THREADS) void k_mpnn(const MpParams p) {
 //   * visits the targets in `order` (grid-cell order): neighbouring targets share sources -> the gathers hit L2.
 // ------------------------------------------------------------------------------------------------
 // (at least 3 waves per SIMD: the D = 464 instance wants 175 VGPRs, seven more than three resident waves leave it)
-#ifndef RGNN_MPNN_WAVES
-#define RGNN_MPNN_WAVES __attribute__((amdgpu_waves_per_eu(3)))
-#endif
 template <int NCH, int DEP, int MODE>
-__global__ __launch_bounds__(MP_THREADS) RGNN_MPNN_WAVES void k_mpnn_fast(const float* __restrict__ P, int64_t ldp,
+__global__ __launch_bounds__(MP_THREADS) __attribute__((amdgpu_waves_per_eu(3))) void k_mpnn_fast(const float* __restrict__ P, int64_t ldp,
                                                          const float* __restrict__ p_bias,
                                                          const float* __restrict__ Q, int64_t ldq,
                                                          const float* __restrict__ We, int64_t ldwe,
@@ -403,7 +385,7 @@ __global__ __launch_bounds__(MP_THREADS) RGNN_MPNN_WAVES void k_mpnn_fast(const 
 // that the two row-register sets swap roles instead of being copied.  With every gather served by the cache the old kernel
 // ran at 232 us of its 263 us (tools/mpnn_bench.py): latency structure, not bandwidth, was the bound.
 template <int NCH, int DEP, bool ARG = false, bool AMAX = false>
-__global__ __launch_bounds__(MP_THREADS) RGNN_MPNN_WAVES void k_mpnn_max(const float* __restrict__ p_bias,
+__global__ __launch_bounds__(MP_THREADS) __attribute__((amdgpu_waves_per_eu(3))) void k_mpnn_max(const float* __restrict__ p_bias,
                                                         const float* __restrict__ Q, int64_t ldq,
                                                         const float* __restrict__ We, int64_t ldwe,
                                                         const float* __restrict__ ea, int de,
@@ -495,40 +477,24 @@ __global__ __launch_bounds__(MP_THREADS) RGNN_MPNN_WAVES void k_mpnn_max(const f
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f);   // empty segment -> exactly 0 (torch-scatter)
         if (cnt > 0) o = make_float4(bias[t].x + acc[t].x, bias[t].y + acc[t].y, bias[t].z + acc[t].z, bias[t].w + acc[t].w);
         if (AMAX) amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
-        if (!(RGNN_MPNN_ABL & 4) || node == 0) {
-#if RGNN_MPNN_NT_STORE
-          // streaming store: the aggregated rows are not read again by this kernel and should not push rows of Q out of L2
-          __builtin_nontemporal_store(o.x, out + (int64_t)node * ldo + ch[t] + 0);
-          __builtin_nontemporal_store(o.y, out + (int64_t)node * ldo + ch[t] + 1);
-          __builtin_nontemporal_store(o.z, out + (int64_t)node * ldo + ch[t] + 2);
-          __builtin_nontemporal_store(o.w, out + (int64_t)node * ldo + ch[t] + 3);
-#else
-          *(float4*)(out + (int64_t)node * ldo + ch[t]) = o;
-#endif
-        }
+        // streaming store: the aggregated rows are not read again by this kernel and should not push rows of Q out of L2
+        // (-27 % HBM reads, -5 % time)
+        __builtin_nontemporal_store(o.x, out + (int64_t)node * ldo + ch[t] + 0);
+        __builtin_nontemporal_store(o.y, out + (int64_t)node * ldo + ch[t] + 1);
+        __builtin_nontemporal_store(o.z, out + (int64_t)node * ldo + ch[t] + 2);
+        __builtin_nontemporal_store(o.w, out + (int64_t)node * ldo + ch[t] + 3);
       }
     };
     open_node(0);
 
     // block of 64 edges: lane j holds the source and the DEP attributes of edge eb + j
-#if RGNN_MPNN_NT_LOAD
-    auto load_src = [&](int eb) { return (eb + lane < e_hi) ? __builtin_nontemporal_load(src + eb + lane) : 0; };
-#else
+    // (streaming loads for this edge stream: -4 % in tools/mpnn_bench.py, nothing inside the step -- plain loads)
     auto load_src = [&](int eb) { return (eb + lane < e_hi) ? src[eb + lane] : 0; };
-#endif
     auto load_ea = [&](int eb, float (&a)[DEP]) {
       const int e = eb + lane;
       if (DEP == 8 && de == 8) {                       // (rows of 32 bytes: two 16-byte loads)
         float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
-#if RGNN_MPNN_NT_LOAD
-        if (e < e_hi) {
-          const float* q_ = ea + (int64_t)e * 8;
-          lo = make_float4(__builtin_nontemporal_load(q_), __builtin_nontemporal_load(q_ + 1), __builtin_nontemporal_load(q_ + 2), __builtin_nontemporal_load(q_ + 3));
-          hi = make_float4(__builtin_nontemporal_load(q_ + 4), __builtin_nontemporal_load(q_ + 5), __builtin_nontemporal_load(q_ + 6), __builtin_nontemporal_load(q_ + 7));
-        }
-#else
         if (e < e_hi) { lo = *(const float4*)(ea + (int64_t)e * 8); hi = *(const float4*)(ea + (int64_t)e * 8 + 4); }
-#endif
         a[0] = lo.x; a[1] = lo.y; a[2] = lo.z; a[3] = lo.w;
         if (DEP == 8) { a[4 % DEP] = hi.x; a[5 % DEP] = hi.y; a[6 % DEP] = hi.z; a[7 % DEP] = hi.w; }
       } else {
@@ -538,22 +504,9 @@ __global__ __launch_bounds__(MP_THREADS) RGNN_MPNN_WAVES void k_mpnn_max(const f
     };
     int src_cur = load_src(e_lo);
     float ea_cur[DEP];
-    if (!RGNN_MPNN_SCALAR_EA) load_ea(e_lo, ea_cur);
-    // RGNN_MPNN_SCALAR_EA (r03 experiment, off): an edge belongs to ONE wave, so the address of its attribute row is wave-uniform
-    // -- the row can come in through the scalar cache, one edge ahead, and the per-edge FMAs take it straight from SGPRs
-    float a_nx[DEP];
-    auto sload_ea = [&](int e, float (&a)[DEP]) {
-      const int ee = __builtin_amdgcn_readfirstlane(min(e, e_hi - 1));
-      const float* r = ea + (int64_t)ee * de;
-      if (de == DEP) {
-#pragma unroll
-        for (int k = 0; k < DEP; k++) a[k] = r[k];
-      } else {
-#pragma unroll
-        for (int k = 0; k < DEP; k++) a[k] = (k < de) ? r[k] : 0.f;
-      }
-    };
-    if (RGNN_MPNN_SCALAR_EA) sload_ea(e_lo, a_nx);
+    load_ea(e_lo, ea_cur);
+    // (An edge's attribute row through the scalar cache, one edge ahead, instead of a 64-edge block in VGPRs + 8 v_readlane per edge
+    //  was built in r03: 54 -> 46 VALU per edge, bit-identical, and SLOWER -- 203 -> 212 us on the C2 graph, tools/mpnn_bench.py.)
     float4 qa[NCH], qb[NCH], qc[NCH], qd[NCH];
     // A block holds 64 edges in its registers but only 60 are consumed before the next block takes over: the gathers run up
     // to five edges ahead (j + 5 <= 61), so they never need the NEXT block's indices.  (Reading a lane of a register whose
@@ -562,12 +515,10 @@ __global__ __launch_bounds__(MP_THREADS) RGNN_MPNN_WAVES void k_mpnn_max(const f
     for (int eb = e_lo; eb < e_hi; eb += BLK) {
       const int src_nxt = load_src(eb + BLK);         // (issued before this block's gathers: the first gather wait absorbs them)
       float ea_nxt[DEP];
-      if (!RGNN_MPNN_SCALAR_EA) load_ea(eb + BLK, ea_nxt);
+      load_ea(eb + BLK, ea_nxt);
       auto row_of = [&](int j, float4* q) {           // Q row of edge eb + j (clamped to the stream; surplus gathers are discarded)
         const int jj = min(j, e_hi - 1 - eb);
-        int s_ = __builtin_amdgcn_readlane(src_cur, jj);
-        if (RGNN_MPNN_ABL & 1) s_ &= 63;             // experiment: every gather hits the same 64 rows
-        const int soff = s_ * ldq4;
+        const int soff = __builtin_amdgcn_readlane(src_cur, jj) * ldq4;
 #pragma unroll
         for (int t = 0; t < NCH; t++) q[t] = mp_buf_load16(rq, ch[t] * 4, soff);
       };
@@ -589,13 +540,9 @@ __global__ __launch_bounds__(MP_THREADS) RGNN_MPNN_WAVES void k_mpnn_max(const f
         }
         float aks[DEP];                               // (all broadcasts first: a v_readlane result needs wait states before a VALU
 #pragma unroll                                        //  instruction may read it, and one s_nop per attribute is an issue slot each)
-        for (int k = 0; k < DEP; k++) {
-          if (RGNN_MPNN_SCALAR_EA) aks[k] = a_nx[k];
-          else aks[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ea_cur[k]), j));
-        }
-        if (RGNN_MPNN_SCALAR_EA) sload_ea(e + 1, a_nx);   // (the next edge of the stream, whichever block or target it is in)
+        for (int k = 0; k < DEP; k++) aks[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ea_cur[k]), j));
 #pragma unroll
-        for (int k = 0; k < ((RGNN_MPNN_ABL & 2) ? 1 : DEP); k++) {
+        for (int k = 0; k < DEP; k++) {
           const mp_f32x2 a2 = mp_f32x2{aks[k], aks[k]};
 #pragma unroll
           for (int t = 0; t < NCH; t++) {
@@ -629,10 +576,8 @@ __global__ __launch_bounds__(MP_THREADS) RGNN_MPNN_WAVES void k_mpnn_max(const f
         if (j + 3 < nbk) edge(j + 3, qd);
       }
       src_cur = src_nxt;
-      if (!RGNN_MPNN_SCALAR_EA) {
 #pragma unroll
-        for (int k = 0; k < DEP; k++) ea_cur[k] = ea_nxt[k];
-      }
+      for (int k = 0; k < DEP; k++) ea_cur[k] = ea_nxt[k];
     }
     for (;;) {                                         // the target that was open when the stream ended, then trailing empty ones
       close_node();

@@ -81,9 +81,6 @@ __device__ __forceinline__ void mt_split_row(const float (&x)[8], mt_u32x4& p1, 
 // LDS addressing.  z is split once per window (its three bf16 terms stay in registers across the channel tiles).
 namespace {
 
-#ifndef RGNN_WIN_ONE_STORE
-#define RGNN_WIN_ONE_STORE 1
-#endif
 constexpr int WN_SLOTS = 512;         // slots per window: 8 streams x 64
 constexpr int WN_THREADS = 256;
 typedef int wn_i32x4 __attribute__((ext_vector_type(4)));
@@ -136,13 +133,10 @@ __global__ __launch_bounds__(256) void k_win_wplanes(const float* __restrict__ W
   t[96] = mt_u32x4{__float_as_uint((p_bias != nullptr && c < d) ? p_bias[c] : 0.f), 0u, 0u, 0u};
 }
 
-// Segments padded to 2 slots instead of 4 (-DRGNN_WIN_PAD=2; r05, tests green): 13 % fewer slots on the r = 1 m graphs, and SLOWER
+// Segments padded to 2 slots instead of 4 (r05, tests green): 13 % fewer slots on the r = 1 m graphs, and SLOWER
 // everywhere -- C2 152 -> 202 us per launch, k = 20: 265 -> 366 -- eight possible segment ends per tile are eight copies of the
 // straight-line end code per tile (the <true> instance spills), whatever the number of ends that occur.  4 it stays.
-#ifndef RGNN_WIN_PAD
-#define RGNN_WIN_PAD 4
-#endif
-constexpr int WN_PAD = RGNN_WIN_PAD;   // a target's slots are padded to a multiple of this (2 or 4): a GROUP of WN_PAD accumulator rows
+constexpr int WN_PAD = 4;              // a target's slots are padded to a multiple of this (2 or 4): a GROUP of WN_PAD accumulator rows
 constexpr int WN_GPT = 16 / WN_PAD;    // groups per 16-slot tile of a stream (a segment can end at every group)
 constexpr int WN_GPS = 64 / WN_PAD;    // groups per stream
 constexpr int WN_TMAX = 512 / WN_PAD;  // targets a window can hold
@@ -330,9 +324,8 @@ __global__ __launch_bounds__(WN_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
       win = nxt; up ^= 1; staged = false;
       continue;
     }
-    // stores this wave issues per channel tile: two (one per half, the exec mask of a half that does not end is empty) per group in
-    // which either of its streams ends a segment
-    const int nst = (RGNN_WIN_ONE_STORE ? 1 : 2) * __builtin_popcount(anyend & ((nt >= 4) ? (WN_GPT == 8 ? 0xffffffffu : 0xffffu) : ((1u << (WN_GPT * nt)) - 1u)));
+    // stores this wave issues per channel tile: one per group in which either of its streams ends a segment
+    const int nst = __builtin_popcount(anyend & ((nt >= 4) ? (WN_GPT == 8 ? 0xffffffffu : 0xffffu) : ((1u << (WN_GPT * nt)) - 1u)));
     if (!staged) stage(0, gp, up, nU8);
     bool staged_next = false;
 
@@ -387,16 +380,10 @@ __global__ __launch_bounds__(WN_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
               const unsigned long long mA = ((endA >> k) & 1u) ? 0xffffffffull : 0ull, mB = ((endB >> k) & 1u) ? 0xffffffff00000000ull : 0ull;
               const int soA = __builtin_amdgcn_readlane(tv, k) + ct * 128, soB = __builtin_amdgcn_readlane(tv, 32 + k) + ct * 128;
               if (!(p.abl & 4)) {
-#if RGNN_WIN_ONE_STORE
                 // ONE store per ending group: the two halves' scalar offsets selected per lane, lanes of a half that does not end masked
                 const int off = (half ? soB : soA) + voffc;
                 asm volatile("s_mov_b64 exec, %3\n\tbuffer_store_dword %0, %1, %2, 0 offen nt\n\ts_mov_b64 exec, -1"
                              : : "v"(v), "v"(off), "s"(ro_l), "s"(mA | mB) : "memory");
-#else
-                asm volatile("s_mov_b64 exec, %4\n\tbuffer_store_dword %0, %1, %2, %3 offen nt\n\t"
-                             "s_mov_b64 exec, %6\n\tbuffer_store_dword %0, %1, %2, %5 offen nt\n\ts_mov_b64 exec, -1"
-                             : : "v"(v), "v"(voffc), "s"(ro_l), "s"(soA), "s"(mA), "s"(soB), "s"(mB) : "memory");
-#endif
               }
               if (AMAX) amax = fmaxf(amax, fabsf(v));           // (a half that does not end contributes a partial maximum: a bound all the same)
               const unsigned long long m64 = mA | mB;

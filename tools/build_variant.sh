@@ -1,6 +1,8 @@
 #!/bin/bash
-# Experiments: a variant of librgnn.so with extra -D flags on ONE source file, linked into tools/var/<name>/librgnn.so.
-#   tools/build_variant.sh <name> <source.hip> "<flags>"      then   LD_LIBRARY_PATH=tools/var/<name> tools/x3_bench.bin
+# Experiments: a variant of librgnn.so with ONE source file rebuilt as it stands in the tree (edit it, build the variant, put the
+# edit back), linked with the other objects of radargnn_amd/build/ into tools/var/<name>/librgnn.so.  The kernels have no build-time
+# switches; <flags> is for compiler options (-save-temps, -mllvm ...), and may be "".
+#   tools/build_variant.sh <name> <source.hip> "<flags>"      then   tools/x3_bench.bin radargnn_amd/librgnn.so tools/var/<name>/librgnn.so
 set -e
 name=$1; src=$2; flags=$3
 root=$(cd "$(dirname "$0")/.." && pwd)
