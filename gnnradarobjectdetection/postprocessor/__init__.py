@@ -1,0 +1,1 @@
+from radargnn_amd.metrics import evaluation_selector  # noqa: F401

@@ -760,6 +760,53 @@ int rgnn_point_iou(const float* boxes_pred, const int64_t* pred_ptr, int64_t n_p
                    int64_t n_gt, int32_t rotated, const float* points, const int64_t* frame_ptr, int64_t n_frames,
                    int32_t max_frame_points, const int64_t* out_ptr, int64_t n_out, double* iou, void* tmp, rgnn_stream_t stream);
 
+/* ---------------------------------------------------------------- evaluation metrics (csrc/metrics.hip)
+ * What the reference's evaluators compute after the post-processor (postprocessor/metrics.py:12-196 on
+ * postprocessor/torchmetrics_mean_ap.py:410-1030), packed over all frames by the offset arrays of rgnn_point_iou: no entry
+ * point here launches per frame or per class.  Only the area range "all" exists (nothing is ever "ignored").
+ *
+ * Aligned box IoU (compute_iou with use_point_iou = False, torchmetrics_mean_ap.py:114: torchvision.ops.box_iou): for frame f,
+ * iou[out_ptr[f] + p * G_f + g] (float32) of [x_min, y_min, x_max, y_max] float32 boxes,
+ * inter / (area_p + area_g - inter) with inter = clamp(min(x2) - max(x1), 0) * clamp(min(y2) - max(y1), 0), all float32, no
+ * fused multiply-add.  A restatement of torchvision's documented formula, NOT pinned by an executed torchvision. */
+int rgnn_box_iou(const float* boxes_pred, const int64_t* pred_ptr, const float* boxes_gt, const int64_t* gt_ptr, int64_t n_frames,
+                 const int64_t* out_ptr, int64_t n_out, float* iou, rgnn_stream_t stream);
+/* Greedy matching (_compute_iou, _evaluate_image, _find_best_gt_match, torchmetrics_mean_ap.py:505-551, 612-747), one wave per
+ * (frame, class of `classes`).  iou: the packed matrices, float64 (iou_is_f32 = 0, rgnn_point_iou) or float32 (1, rgnn_box_iou).
+ * The class's detections of the frame by descending score (ties: ascending position -- the reference's torch.sort leaves ties
+ * unpinned; NaN first), cut to max_det; for every threshold, in that order: the maximum over the class's ground-truth boxes of
+ * (0 if already matched, else the IoU), lowest position on ties; matched iff it is strictly greater than the threshold (float64
+ * comparison; for float32 IoUs the threshold is rounded to float32 first).  rank: [dev] int32 [n_pred], the detection's rank in
+ * its (frame, class) list or -1 beyond max_det; matched: [dev] uint8 [n_thresholds, n_pred].  Both are cleared here.
+ * Capacity: rgnn_map_match_capacity() (2048) detections and as many ground-truth boxes of ONE class in one frame.  The lists
+ * are counted on the device: a longer one sets bit 0 of *status ([dev] int32, cleared here) and that (frame, class) pair is
+ * left unmatched with rank -1; the caller reads the word and refuses the result. */
+int32_t rgnn_map_match_capacity(void);
+int rgnn_map_match(const void* iou, int32_t iou_is_f32, const int64_t* pred_ptr, const int64_t* gt_ptr, const int64_t* out_ptr,
+                   int64_t n_frames, const int32_t* det_labels, const float* det_scores,
+                   int64_t n_pred, const int32_t* gt_labels, const int32_t* classes, int32_t n_classes, const double* thresholds,
+                   int32_t n_thresholds, int32_t max_det, int32_t* rank, uint8_t* matched, int32_t* status, rgnn_stream_t stream);
+/* Recall / precision / score tables (__calculate_recall_precision_scores, torchmetrics_mean_ap.py:898-973), one work-group per
+ * (class, threshold, max_det).  order: [dev] int64 [n_pred], the detections class by class in the order of `classes`, inside a
+ * class by descending score, stable (two passes of rgnn_sort_scores); cls_ptr: [dev] int64 [2, n_classes], where each class
+ * begins and ends in `order` (a work-group reads its own class's segment only);
+ * rank / matched: from rgnn_map_match; max_dets: [dev] int32 [n_max_dets]; rec: [dev] float32 [n_rec] ascending recall
+ * thresholds (at most 1024).  Per curve: the class's detections with rank < max_det in that order, tp / fp running counts as
+ * float32, rc = tp / npig, pr = tp / (fp + tp + 2.220446049250313e-16) (IEEE division), pr made non-increasing by the running
+ * maximum from the right, and per recall threshold r the first index with rc >= r.
+ * precision, scores: [dev] float32 [n_thresholds, n_rec, n_classes, n_max_dets]; recall: [dev] float32 [n_thresholds, n_classes,
+ * n_max_dets]; every entry is written: -1 for a class without ground truth, else the value or 0. */
+int rgnn_map_curves(const int64_t* order, const int64_t* cls_ptr, const int32_t* det_labels, const float* det_scores, const int32_t* rank,
+                    const uint8_t* matched, int64_t n_pred, const int32_t* gt_labels, int64_t n_gt, const int32_t* classes,
+                    int32_t n_classes, int32_t n_thresholds, const int32_t* max_dets, int32_t n_max_dets, const float* rec,
+                    int32_t n_rec, float* precision, float* scores, float* recall, rgnn_stream_t stream);
+/* Confusion matrix of the node labels (SegmentationMetrics, metrics.py:136-196: sklearn's confusion_matrix with
+ * labels = range(n_classes)): matrix [dev] int64 [n_classes, n_classes], rows = true label, columns = predicted label, cleared
+ * here.  y_true / y_pred: [dev] float64 [n], truncated towards zero (astype(int)); a node with a label outside
+ * 0 .. n_classes - 1 is left out; a NaN label sets bit 0 of *status ([dev] int32, cleared here).  At most 64 classes. */
+int rgnn_confusion_matrix(const double* y_true, const double* y_pred, int64_t n, int32_t n_classes, int64_t* matrix,
+                          int32_t* status, rgnn_stream_t stream);
+
 /* ================================================================ backward pass (training: gnn/trainer.py:176-231)
  * What autograd derives for the reference's op-by-op forward, for the fused forward kernels above.  The dense-layer
  * gradients are GEMMs: dX = dY W runs on rgnn_linear_fwd with the transposed weight, dW = dY^T X on rgnn_wgrad

@@ -178,6 +178,13 @@ SIGNATURES = {
     "rgnn_remove_duplicate_boxes": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "rgnn_point_iou_tmp_bytes": (c_i64, [c_i64, c_i32, c_i64, c_i64]),
     "rgnn_point_iou": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "rgnn_box_iou": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "rgnn_map_match_capacity": (c_i32, []),
+    "rgnn_map_match": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_i32,
+                               c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_map_curves": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32,
+                                c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_confusion_matrix": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "rgnn_detection_loss_blocks": (c_i64, [c_i64]),
     "rgnn_detection_loss": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_i32, c_f32, c_f32, c_f32,
                                     c_vp, c_vp, c_vp, c_vp]),

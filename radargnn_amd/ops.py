@@ -1970,6 +1970,130 @@ def point_iou(boxes_pred: torch.Tensor, pred_ptr: Sequence[int], boxes_gt: torch
     return iou, out
 
 
+# ---- evaluation metrics: box IoU, mAP matching and curves, confusion matrix (csrc/metrics.hip) -------------------------
+def _offsets_dev(device, *lists) -> torch.Tensor:
+    return torch.tensor([[int(v) for v in l] for l in lists], dtype=torch.int64).to(device)
+
+
+def _matrix_offsets(pp: Sequence[int], gp: Sequence[int]):
+    if len(pp) < 2 or len(pp) != len(gp):
+        raise ValueError("pred_ptr and gt_ptr need one offset per frame plus one")
+    out = [0]
+    for f in range(len(pp) - 1):
+        out.append(out[-1] + (pp[f + 1] - pp[f]) * (gp[f + 1] - gp[f]))
+    return out
+
+
+def box_iou(boxes_pred: torch.Tensor, pred_ptr: Sequence[int], boxes_gt: torch.Tensor, gt_ptr: Sequence[int]):
+    """Aligned box IoU matrices of a batch of frames (rgnn_box_iou) -> (iou f32 [sum P_f G_f], matrix offsets [B + 1] as a list),
+    the layout of ``point_iou``.  ``boxes_*``: float32 [M, 4] [x_min, y_min, x_max, y_max]."""
+    boxes_pred = _dev(boxes_pred, "boxes_pred", torch.float32).contiguous()
+    boxes_gt = _dev(boxes_gt, "boxes_gt", torch.float32).contiguous()
+    pp, gp = [int(v) for v in pred_ptr], [int(v) for v in gt_ptr]
+    out = _matrix_offsets(pp, gp)
+    if boxes_pred.dim() != 2 or boxes_pred.shape[1] != 4 or boxes_gt.dim() != 2 or boxes_gt.shape[1] != 4:
+        raise ValueError("boxes must be [M, 4]")
+    if pp[-1] != boxes_pred.shape[0] or gp[-1] != boxes_gt.shape[0]:
+        raise ValueError("the offsets must end at the number of boxes")
+    dev = boxes_pred.device
+    iou = torch.empty(out[-1], dtype=torch.float32, device=dev)
+    ptrs = _offsets_dev(dev, pp, gp, out)
+    check(lib.rgnn_box_iou(_ptr(boxes_pred), _ptr(ptrs[0]), _ptr(boxes_gt), _ptr(ptrs[1]), len(pp) - 1, _ptr(ptrs[2]), out[-1],
+                           _ptr(iou), _stream()))
+    return iou, out
+
+
+def map_match(iou: torch.Tensor, pred_ptr: Sequence[int], gt_ptr: Sequence[int], det_labels: torch.Tensor, det_scores: torch.Tensor,
+              gt_labels: torch.Tensor, classes: torch.Tensor, iou_thresholds: Sequence[float], max_det: int = 100):
+    """Greedy matching of every (frame, class) in one launch (rgnn_map_match) -> (rank int32 [n_pred]: the detection's place in
+    its frame's class list by descending score, -1 beyond ``max_det``; matched uint8 [T, n_pred]).  ``iou``: the packed matrices
+    of ``point_iou`` (float64) or ``box_iou`` (float32); labels and ``classes`` int32, scores float32, all on the device.
+    More than ``rgnn_map_match_capacity()`` detections or ground-truth boxes of one class in one frame raise RgnnError (the
+    kernel's status word, one host read)."""
+    _dev(iou, "iou")
+    if iou.dtype not in (torch.float32, torch.float64):
+        raise TypeError("iou must be float32 (box IoU) or float64 (point IoU)")
+    iou = iou.contiguous()
+    det_labels = _dev(det_labels, "det_labels", torch.int32).contiguous()
+    det_scores = _dev(det_scores, "det_scores", torch.float32).contiguous()
+    gt_labels = _dev(gt_labels, "gt_labels", torch.int32).contiguous()
+    classes = _dev(classes, "classes", torch.int32).contiguous()
+    pp, gp = [int(v) for v in pred_ptr], [int(v) for v in gt_ptr]
+    out = _matrix_offsets(pp, gp)
+    b, n_pred = len(pp) - 1, pp[-1]
+    if det_labels.shape != (n_pred,) or det_scores.shape != (n_pred,) or gt_labels.shape != (gp[-1],) or iou.shape != (out[-1],):
+        raise ValueError("one label and score per detection, one label per ground-truth box, one IoU per pair")
+    thr = torch.tensor([float(t) for t in iou_thresholds], dtype=torch.float64)
+    dev = det_labels.device
+    rank = torch.empty(n_pred, dtype=torch.int32, device=dev)
+    matched = torch.empty((thr.numel(), n_pred), dtype=torch.uint8, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ptrs = _offsets_dev(dev, pp, gp, out)
+    thr = thr.to(dev)
+    check(lib.rgnn_map_match(_ptr(iou), 1 if iou.dtype == torch.float32 else 0, _ptr(ptrs[0]), _ptr(ptrs[1]), _ptr(ptrs[2]), b,
+                             _ptr(det_labels), _ptr(det_scores), n_pred, _ptr(gt_labels), _ptr(classes), classes.numel(), _ptr(thr),
+                             thr.numel(), int(max_det), _ptr(rank), _ptr(matched), _ptr(status), _stream()))
+    if int(status.item()) & 1:
+        cap = int(lib.rgnn_map_match_capacity())
+        raise RgnnError(f"rgnn_map_match: at most {cap} detections and {cap} ground-truth boxes of one class per frame")
+    return rank, matched
+
+
+def map_curves(det_labels: torch.Tensor, det_scores: torch.Tensor, rank: torch.Tensor, matched: torch.Tensor, gt_labels: torch.Tensor,
+               classes: torch.Tensor, max_dets: Sequence[int] = (1, 10, 100), rec_thresholds: Optional[torch.Tensor] = None):
+    """The mAP's tables in one launch after two sorts (rgnn_sort_scores by score, then by class; rgnn_map_curves) -> (precision f32 [T, R, K, M],
+    scores f32 [T, R, K, M], recall f32 [T, K, M]); -1 for a class without ground truth.  ``rank`` / ``matched`` from ``map_match``;
+    ``rec_thresholds``: ascending float32 [R], default ``torch.linspace(0, 1, 101)``."""
+    det_labels = _dev(det_labels, "det_labels", torch.int32).contiguous()
+    det_scores = _dev(det_scores, "det_scores", torch.float32).contiguous()
+    rank = _dev(rank, "rank", torch.int32).contiguous()
+    matched = _dev(matched, "matched", torch.uint8).contiguous()
+    gt_labels = _dev(gt_labels, "gt_labels", torch.int32).contiguous()
+    classes = _dev(classes, "classes", torch.int32).contiguous()
+    n_pred, dev = det_labels.numel(), det_labels.device
+    if det_scores.shape != (n_pred,) or rank.shape != (n_pred,) or matched.dim() != 2 or matched.shape[1] != n_pred:
+        raise ValueError("one score and rank per detection; matched is [T, n_pred]")
+    rec = torch.linspace(0.0, 1.0, 101) if rec_thresholds is None else torch.as_tensor(rec_thresholds, dtype=torch.float32).cpu()
+    if rec.dim() != 1 or rec.numel() < 1 or bool((rec[1:] < rec[:-1]).any()):
+        raise ValueError("rec_thresholds must be a non-empty ascending vector")
+    rec = rec.to(dev)
+    md = torch.tensor(sorted(int(m) for m in max_dets), dtype=torch.int32).to(dev)
+    t, k, m, r = matched.shape[0], classes.numel(), md.numel(), rec.numel()
+    if k > 1 and bool((classes[1:] <= classes[:-1]).any()):
+        raise ValueError("classes must be strictly ascending")
+    # class by class (ascending, like `classes`), inside a class by descending score: a stable sort by class of the score order
+    order = sort_scores(det_scores)
+    order = order.index_select(0, sort_scores(-det_labels.index_select(0, order).to(torch.float64)))
+    by_class = det_labels.index_select(0, order)
+    cls_ptr = torch.stack((torch.searchsorted(by_class, classes), torch.searchsorted(by_class, classes, right=True))).to(torch.int64)
+    cls_ptr = cls_ptr.contiguous()                                        # [2, K]: first and one-past-last place of each class
+    precision = torch.empty((t, r, k, m), dtype=torch.float32, device=dev)
+    scores = torch.empty((t, r, k, m), dtype=torch.float32, device=dev)
+    recall = torch.empty((t, k, m), dtype=torch.float32, device=dev)
+    check(lib.rgnn_map_curves(_ptr(order), _ptr(cls_ptr), _ptr(det_labels), _ptr(det_scores), _ptr(rank), _ptr(matched), n_pred, _ptr(gt_labels),
+                              gt_labels.numel(), _ptr(classes), k, t, _ptr(md), m, _ptr(rec), r, _ptr(precision), _ptr(scores),
+                              _ptr(recall), _stream()))
+    return precision, scores, recall
+
+
+def confusion_matrix(y_true: torch.Tensor, y_pred: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """int64 [K, K] on the device, rows = true label, columns = predicted label (rgnn_confusion_matrix): labels truncated like
+    ``astype(int)``, nodes with a label outside 0 .. K-1 left out.  A NaN label raises ValueError (the kernel's status word, one
+    host read)."""
+    _dev(y_true, "y_true")
+    _dev(y_pred, "y_pred")
+    yt, yp = y_true.reshape(-1).to(torch.float64).contiguous(), y_pred.reshape(-1).to(torch.float64).contiguous()
+    if yt.numel() != yp.numel():
+        raise ValueError("one predicted label per true label")
+    k = int(num_classes)
+    matrix = torch.empty((max(k, 0), max(k, 0)), dtype=torch.int64, device=yt.device)
+    status = torch.empty(1, dtype=torch.int32, device=yt.device)
+    check(lib.rgnn_confusion_matrix(_ptr(yt), _ptr(yp), yt.numel(), k, _ptr(matrix), _ptr(status), _stream()))
+    if int(status.item()) & 1:
+        raise ValueError("Input contains NaN.")                # what sklearn's input check raises
+    return matrix
+
+
 # ---- detection loss (csrc/loss.hip) ----------------------------------------------------------------------------------
 def detection_loss(cls: torch.Tensor, boxes: torch.Tensor, y: torch.Tensor, class_weight: Optional[torch.Tensor],
                    bg_index: int, delta: float, cls_loss_weight: float, bb_loss_weight: float):
