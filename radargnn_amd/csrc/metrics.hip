@@ -7,8 +7,10 @@
 // is launched per frame or per class.  Only the area range "all" exists: no ground-truth box and no detection is ever
 // "ignored" (true for finite boxes; the COCO pixel ranges small / medium / large mean nothing in metres).
 //
-// UNPINNED: the box IoU restates torchvision.ops.box_iou from its documented formula; torchvision was never executed
-// against it.  The reference orders equal scores with an unstable torch.sort; here ties go by ascending position.
+// UNPINNED: the box IoU restates torchvision.ops.box_iou from its documented formula; it was never executed against
+// torchvision (the restatement it is compared with bit for bit is held to a float64 evaluation of the same geometry).
+// The reference orders equal scores with an unstable torch.sort.  This project decides, and tests/test_gpu_metrics_edges.py
+// holds it: the order is that of torch.sort(descending, stable) -- NaN first, -0.0 and 0.0 tie, ties by ascending position.
 // The file is built with -ffp-contract=off like the rest of the library: no fused multiply-adds.
 #include "common.h"
 #include <math.h>

@@ -1,11 +1,13 @@
 """numpy restatement of the reference's evaluation metrics, for the cases the committed fixtures do not cover and as the host-side
 baseline of the device path: the greedy matching and the recall / precision tables of the vendored ``MeanAveragePrecision``
 (postprocessor/torchmetrics_mean_ap.py:505-551, 612-747, 898-1030; area range "all" only), ``torchvision.ops.box_iou``'s formula
-(unpinned: torchvision was never executed), and the confusion matrix / F1 of ``SegmentationMetrics`` (postprocessor/metrics.py:136-196).
+(never executed against torchvision; held to a float64 evaluation of the same geometry), and the confusion matrix / F1 of
+``SegmentationMetrics`` (postprocessor/metrics.py:136-196).
 Checked against the reference-generated tests/golden/eval_map_*.npz and against scikit-learn by tests/test_map_oracle.py.
 
-Ties between equal scores are unpinned in the reference (an unstable torch.sort); here, as in the kernels, they go by ascending
-position.  Scores must not be NaN."""
+The reference orders equal scores with an unstable torch.sort.  This project decides: the order of scores is that of
+``torch.sort(scores, descending=True, stable=True)`` -- NaN first, -0.0 and 0.0 tie, equal scores (NaNs among themselves too) by
+ascending position -- here and in the kernels; tests/test_map_oracle.py holds ``order_desc`` to it."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence
@@ -23,19 +25,40 @@ def rec_thresholds() -> np.ndarray:
 
 
 def order_desc(scores: np.ndarray) -> np.ndarray:
-    return np.argsort(-np.asarray(scores, dtype=np.float64), kind="stable")
+    """Positions by descending score as ``torch.sort(scores, descending=True, stable=True)`` orders them: NaN first, -0.0 and 0.0
+    tie, ties (the NaNs too) by ascending position."""
+    s = np.asarray(scores, dtype=np.float64).reshape(-1)
+    nan = np.isnan(s)
+    rest = np.argsort(np.where(nan, 0.0, -s), kind="stable")
+    return np.concatenate((np.nonzero(nan)[0], rest[~nan[rest]]))
 
 
 def box_iou(bp: np.ndarray, bg: np.ndarray) -> np.ndarray:
     """float32 [P, G] of [x_min, y_min, x_max, y_max] float32 boxes, every operation rounded to float32."""
     a, b = np.asarray(bp, dtype=np.float32).reshape(-1, 1, 4), np.asarray(bg, dtype=np.float32).reshape(1, -1, 4)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        area_a = (a[..., 2] - a[..., 0]) * (a[..., 3] - a[..., 1])
+        area_b = (b[..., 2] - b[..., 0]) * (b[..., 3] - b[..., 1])
+        w = np.minimum(a[..., 2], b[..., 2]) - np.maximum(a[..., 0], b[..., 0])
+        h = np.minimum(a[..., 3], b[..., 3]) - np.maximum(a[..., 1], b[..., 1])
+        inter = np.maximum(w, np.float32(0)) * np.maximum(h, np.float32(0))
+        return (inter / ((area_a + area_b) - inter)).astype(np.float32)
+
+
+def box_iou_float64(bp: np.ndarray, bg: np.ndarray) -> np.ndarray:
+    """The same geometry from the same float32 corners, every operation in float64: what ``box_iou`` is judged by."""
+    a, b = np.asarray(bp, dtype=np.float64).reshape(-1, 1, 4), np.asarray(bg, dtype=np.float64).reshape(1, -1, 4)
     area_a = (a[..., 2] - a[..., 0]) * (a[..., 3] - a[..., 1])
     area_b = (b[..., 2] - b[..., 0]) * (b[..., 3] - b[..., 1])
-    w = np.minimum(a[..., 2], b[..., 2]) - np.maximum(a[..., 0], b[..., 0])
-    h = np.minimum(a[..., 3], b[..., 3]) - np.maximum(a[..., 1], b[..., 1])
-    inter = np.maximum(w, np.float32(0)) * np.maximum(h, np.float32(0))
-    with np.errstate(invalid="ignore", divide="ignore"):
-        return (inter / ((area_a + area_b) - inter)).astype(np.float32)
+    w = np.clip(np.minimum(a[..., 2], b[..., 2]) - np.maximum(a[..., 0], b[..., 0]), 0.0, None)
+    h = np.clip(np.minimum(a[..., 3], b[..., 3]) - np.maximum(a[..., 1], b[..., 1]), 0.0, None)
+    return w * h / (area_a + area_b - w * h)
+
+
+def well_conditioned_boxes(rng: np.random.Generator, n: int) -> np.ndarray:
+    """float32 [n, 4] boxes with centres in [-8, 8]^2 and sides in [0.5, 10]: more than a fifth of all pairs overlap."""
+    centre, side = rng.uniform(-8.0, 8.0, size=(n, 2)), rng.uniform(0.5, 10.0, size=(n, 2))
+    return np.concatenate((centre - side / 2, centre + side / 2), axis=1).astype(np.float32)
 
 
 def match_frame(iou: np.ndarray, det_labels, det_scores, gt_labels, classes: Sequence[int], thresholds: Sequence[float],
