@@ -44,6 +44,9 @@ typedef void* rgnn_stream_t; /* hipStream_t */
 #define RGNN_STATUS_EDGE_COUNT_CHANGED 8 /* rgnn_radius_graph_fill_checked: rowptr[n] != the n_edges the caller sized for */
 #define RGNN_STATUS_NOT_SYMMETRIC 16     /* rgnn_csr_by_target_symmetric: an edge (s,t) without its twin (t,s)               */
 #define RGNN_STATUS_SPLITK_TIMEOUT 32    /* a dense launch gave up waiting for a partial tile of another work-group (see splitk_ws) */
+#define RGNN_STATUS_GT_OBJECT_TOO_LARGE 64   /* rgnn_create_gt_boxes: an object of more than rgnn_gt_object_cap() points; its rows are not written */
+#define RGNN_STATUS_GT_DEGENERATE_OBJECT 128 /* rgnn_create_gt_boxes: two coincident points, or >= 3 points whose hull has no area (the reference
+                                              * divides by zero / raises QhullError); its rows are not written */
 
 #define RGNN_SPLITK_TIMEOUT_WORD 1000    /* index of the time-out counter in the flag area of rgnn_linear_args.splitk_ws */
 
@@ -938,6 +941,29 @@ int rgnn_detection_loss_bwd(const float* cls, int64_t ldc, int32_t n_classes, co
                             int32_t bg_index, float delta, float cls_loss_weight, float bb_loss_weight, const double* sums,
                             const float* grad_loss, float* d_cls, int64_t lddc, float* d_boxes, int64_t lddb,
                             rgnn_stream_t stream);
+
+/* ================================================================ ground-truth box targets (csrc/groundtruth.hip)
+ * GroundTruthCreator.create_2D_bounding_boxes (preprocessor/radarscenes/dataset_creation.py:232-521): the box columns of `y`, the
+ * inverse of rgnn_decode_ground_truth.  The objects of the whole batch come in CSR form: object o owns the point rows
+ * obj_rows[obj_ptr[o] .. obj_ptr[o + 1]) (int32 [n_rows], ascending inside an object: "p1" of a two-point object is the lower
+ * row); pos: float64 [n, 2].  Per object: aligned != 0: the min / max box of its points (utils/math.py:284-299); otherwise the
+ * minimum-area rectangle flush with an edge of the convex hull (utils/math.py:304-439; 1 point: a 0.5 x 0.5 box at the point,
+ * 2 points: midpoint, their distance x 0.5 along p2 - p1).  Per point of the object, out[row] (float64, [n, 4] aligned or [n, 5]):
+ *   aligned                 [x_c - x, y_c - y, dx, dy]
+ *   invariance 0 none       [x_c, y_c, l, w, theta]            (theta of the long side in rad, [0, pi))
+ *   invariance 1 translation[x_c - x, y_c - y, l, w, theta]
+ *   invariance 2 en         [d, angle(nn -> centre), l, w, angle(nn -> long side)]  (bounding_box.py:205-272; nn_index int32 [n]: the
+ *                           nearest other point of every point's frame, rgnn_knn_graph with k = 1; may be NULL otherwise)
+ * Rows of points that belong to no object are NOT written: the caller pre-fills out (and rect) with NaN.
+ * rect (optional): float64 [n_obj, 5], the object's absolute rectangle [x_c, y_c, l, w, theta in degrees, 0 <= theta < 180]
+ * (aligned: [x_c, y_c, dx, dy, 0]).
+ * An object of more than rgnn_gt_object_cap() (1024) points, a degenerate one (see the status bits), or one whose offsets / rows
+ * point outside the arrays is left unwritten and raises its bit in *status; all other objects are written as usual.
+ * One launch (one wave per object), no synchronisation; the result does not depend on scheduling. */
+int32_t rgnn_gt_object_cap(void);
+int rgnn_create_gt_boxes(const double* pos, int64_t n, const int64_t* obj_ptr, const int32_t* obj_rows, int64_t n_rows,
+                         int64_t n_obj, const int32_t* nn_index /*[dev] or NULL*/, int32_t aligned, int32_t invariance,
+                         double* out, double* rect /*[dev] or NULL*/, int32_t* status /*[dev]*/, rgnn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -193,6 +193,8 @@ SIGNATURES = {
     "rgnn_collate_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "rgnn_collate_edges": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_i64, c_vp]),
     "rgnn_stage_frames": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_i64]),
+    "rgnn_gt_object_cap": (c_i32, []),
+    "rgnn_create_gt_boxes": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
 }
 
 

@@ -184,6 +184,8 @@ STATUS_TIME_INDEX_OVERFLOW = 4
 STATUS_EDGE_COUNT_CHANGED = 8
 STATUS_NOT_SYMMETRIC = 16
 STATUS_SPLITK_TIMEOUT = 32
+STATUS_GT_OBJECT_TOO_LARGE = 64
+STATUS_GT_DEGENERATE_OBJECT = 128
 SPLITK_TIMEOUT_WORD = 1000          # rgnn.h RGNN_SPLITK_TIMEOUT_WORD
 
 
@@ -1927,6 +1929,68 @@ def decode_ground_truth(labels: torch.Tensor, boxes: torch.Tensor, pos: torch.Te
                                        _ld(boxes) if n > 1 else boxes.shape[1], boxes.shape[1], _ptr(pos), _ptr(nn_index), n,
                                        int(bg_index), int(invariance), _ptr(keep), _ptr(corners), _stream()))
     return keep, corners
+
+
+def gt_object_cap() -> int:
+    """Points of one object ``create_gt_boxes`` takes (rgnn_gt_object_cap); a larger one sets STATUS_GT_OBJECT_TOO_LARGE."""
+    return int(lib.rgnn_gt_object_cap())
+
+
+def group_objects(object_id: torch.Tensor, frame_ptr: torch.Tensor):
+    """The objects of a batch of frames in CSR form -> (obj_ptr int64 [n_obj + 1], obj_rows int32 [rows of all objects]).
+    ``object_id``: int tensor [N], negative = background; ids are local to a frame (frame f = rows
+    [frame_ptr[f], frame_ptr[f + 1])) and need not be dense.  Objects are ordered by (frame, id); inside an object the rows
+    ascend (two stable device sorts).  ``obj_rows`` has N entries: the background rows follow the last object and belong to
+    nobody.  No loop over frames; one host read (the number of objects)."""
+    _dev(object_id, "object_id")
+    _dev(frame_ptr, "frame_ptr", torch.int64)
+    if object_id.dim() != 1 or object_id.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64):
+        raise ValueError("object_id must be an int tensor [N]")
+    dev, n = object_id.device, object_id.numel()
+    ids = object_id.to(torch.int64)
+    fg = ids >= 0
+    rows = torch.arange(n, dtype=torch.int64, device=dev)
+    frame = torch.bucketize(rows, frame_ptr[1:].contiguous(), right=True)
+    frame = torch.where(fg, frame, torch.full_like(frame, frame_ptr.numel()))       # background behind every frame
+    by_id = torch.sort(ids, stable=True).indices
+    by_frame = torch.sort(frame.index_select(0, by_id), stable=True).indices
+    rows = by_id.index_select(0, by_frame)
+    ids, frame, fg = ids.index_select(0, rows), frame.index_select(0, rows), fg.index_select(0, rows)
+    first = fg.clone()
+    if n > 1:
+        first[1:] &= (ids[1:] != ids[:-1]) | (frame[1:] != frame[:-1])
+    starts = torch.nonzero(first, as_tuple=False).view(-1)                          # the host read: n_obj
+    obj_ptr = torch.cat((starts, fg.sum(dtype=torch.int64).view(1)))
+    return obj_ptr, rows.to(torch.int32)
+
+
+def create_gt_boxes(pos: torch.Tensor, obj_ptr: torch.Tensor, obj_rows: torch.Tensor, nn_index: Optional[torch.Tensor],
+                    aligned: bool, invariance: int, want_rect: bool = False, status: Optional[torch.Tensor] = None):
+    """-> (boxes f64 [N, 4|5] with NaN rows for points of no object, rect f64 [n_obj, 5] | None, status int32 [1])
+    (rgnn_create_gt_boxes).  ``pos`` f64 [N, 2]; ``obj_ptr`` / ``obj_rows``: ``group_objects``; ``nn_index`` int32 [N] for the
+    en encoding (invariance 2, rotated boxes).  Objects the kernel refuses (STATUS_GT_OBJECT_TOO_LARGE,
+    STATUS_GT_DEGENERATE_OBJECT in ``status``) keep NaN rows; the caller reads ``status``."""
+    _dev(pos, "pos", torch.float64)
+    _dev(obj_ptr, "obj_ptr", torch.int64)
+    _dev(obj_rows, "obj_rows", torch.int32)
+    if pos.dim() != 2 or pos.shape[1] != 2 or not pos.is_contiguous():
+        raise ValueError("pos must be contiguous [N, 2]")
+    if obj_ptr.dim() != 1 or obj_ptr.numel() < 1 or obj_rows.dim() != 1:
+        raise ValueError("obj_ptr must be [n_obj + 1], obj_rows 1-D")
+    n, n_obj = pos.shape[0], obj_ptr.numel() - 1
+    if nn_index is not None:
+        _dev(nn_index, "nn_index", torch.int32)
+        if nn_index.shape != (n,):
+            raise ValueError("nn_index must be [N]")
+        nn_index = nn_index.contiguous()
+    obj_ptr, obj_rows = obj_ptr.contiguous(), obj_rows.contiguous()
+    out = torch.full((n, 4 if aligned else 5), float("nan"), dtype=torch.float64, device=pos.device)
+    rect = torch.full((n_obj, 5), float("nan"), dtype=torch.float64, device=pos.device) if want_rect else None
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=pos.device)
+    check(lib.rgnn_create_gt_boxes(_ptr(pos), n, _ptr(obj_ptr), _ptr(obj_rows), obj_rows.numel(), n_obj, _ptr(nn_index),
+                                   1 if aligned else 0, int(invariance), _ptr(out), _ptr(rect), _ptr(status), _stream()))
+    return out, rect, status
 
 
 def remove_duplicate_boxes(corners: torch.Tensor, box_ptr: torch.Tensor) -> torch.Tensor:

@@ -30,7 +30,7 @@ def _f32(a: np.ndarray) -> np.ndarray:
 
 
 def _clustered_frame(rng: np.random.Generator, n_clusters: int, pts_per_cluster: int, n_clutter: int,
-                     x_range, y_range, n_timestamps: int) -> RadarFrame:
+                     x_range, y_range, n_timestamps: int, with_object_id: bool = False):
     xs, vs = [], []
     for _ in range(n_clusters):
         centre = np.array([rng.uniform(*x_range), rng.uniform(*y_range)])
@@ -53,7 +53,11 @@ def _clustered_frame(rng: np.random.Generator, n_clusters: int, pts_per_cluster:
     rcs = rng.normal(-5.0, 10.0, size=(n, 1))
     t_base = 1.0e6 + np.arange(n_timestamps, dtype=np.float64) * 17.0
     timestamp = t_base[rng.integers(0, n_timestamps, size=n)].reshape(n, 1)
-    return RadarFrame(_f32(X), _f32(V), _f32(rcs), _f32(timestamp))
+    frame = RadarFrame(_f32(X), _f32(V), _f32(rcs), _f32(timestamp))
+    if with_object_id:                                           # cluster membership of every row, -1 = clutter
+        member = np.concatenate((np.repeat(np.arange(n_clusters, dtype=np.int64), pts_per_cluster), np.full(n_clutter, -1, dtype=np.int64)))
+        return frame, member[perm]
+    return frame
 
 
 def radarscenes_frame(frame_idx: int = 0, n_clusters: int = 40, pts_per_cluster: int = 35,
@@ -62,6 +66,14 @@ def radarscenes_frame(frame_idx: int = 0, n_clusters: int = 40, pts_per_cluster:
     (``configurations/configuration_radarscenes.yml:8``)."""
     rng = np.random.Generator(np.random.PCG64(1234 + frame_idx))
     return _clustered_frame(rng, n_clusters, pts_per_cluster, n_clutter, (0.0, 100.0), (-50.0, 50.0), 30)
+
+
+def radarscenes_frame_with_objects(frame_idx: int = 0, n_clusters: int = 40, pts_per_cluster: int = 35, n_clutter: int = 1600):
+    """``radarscenes_frame`` (the same frame, bit for bit) plus ``object_id`` int64 [N]: the cluster every point was drawn from,
+    -1 for clutter -- the input of ``radargnn_amd.groundtruth.create_2d_bounding_boxes_batched``, so that training tools can
+    run on real box targets."""
+    rng = np.random.Generator(np.random.PCG64(1234 + frame_idx))
+    return _clustered_frame(rng, n_clusters, pts_per_cluster, n_clutter, (0.0, 100.0), (-50.0, 50.0), 30, with_object_id=True)
 
 
 def nuscenes_frame(frame_idx: int = 0) -> RadarFrame:
