@@ -14,10 +14,10 @@ import torch
 
 
 def detection_loss(cls: torch.Tensor, bb: torch.Tensor, y: torch.Tensor, bg_index: int, class_weights=None,
-                   cls_loss_weight: float = 1.0, bb_loss_weight: float = 1.0):
+                   cls_loss_weight: float = 1.0, bb_loss_weight: float = 1.0, delta: float = 1.0):
     weights = None if class_weights is None else torch.as_tensor(class_weights, dtype=cls.dtype)
     cross_entropy = torch.nn.CrossEntropyLoss(weight=weights)
-    huber = torch.nn.HuberLoss()
+    huber = torch.nn.HuberLoss(delta=delta)
     label_true = y[:, 0].long()
     bb_true = y[:, 1:]
     loss_cls = cross_entropy(cls, label_true)
@@ -42,14 +42,19 @@ def detection_loss_vectorised(cls: torch.Tensor, bb: torch.Tensor, y: torch.Tens
     10^5 rows of a training batch.  Same function term by term:
 
     * weighted cross-entropy, mean reduction: sum_i w[y_i] (-log softmax(cls_i)[y_i]) / sum_i w[y_i];
-    * HuberLoss() (mean over the W box components) per row whose label is not ``bg_index``, averaged over those rows;
+    * a label of -100 (``CrossEntropyLoss``'s ``ignore_index``): weight 0 in the numerator and the denominator of the cross
+      entropy (no gradient to that row's logits); the row is still an object row of the box term, as in the per-node loop;
+    * HuberLoss(delta) (mean over the W box components) per row whose label is not ``bg_index``, averaged over those rows;
     * no such row, or a NaN box term: the box term is 0 (and contributes no gradient)."""
     label = y[:, 0].long()
     w = torch.ones(cls.shape[1], dtype=cls.dtype, device=cls.device) if class_weights is None else \
         torch.as_tensor(class_weights, dtype=cls.dtype).to(cls.device)
-    wi = w[label]
-    nll = -torch.log_softmax(cls, dim=1).gather(1, label.view(-1, 1)).view(-1)
-    loss_cls = (wi * nll).sum() / wi.sum()
+    ignored = label == -100
+    safe = label.masked_fill(ignored, 0)
+    wi = w[safe].masked_fill(ignored, 0.0)
+    nll = -torch.log_softmax(cls, dim=1).gather(1, safe.view(-1, 1)).view(-1)
+    # (sum over the kept rows only: 0 * inf of an ignored row must not reach the numerator)
+    loss_cls = (wi * nll)[~ignored].sum() / wi.sum()
     obj = label != bg_index
     loss_bb = torch.zeros((), dtype=cls.dtype, device=cls.device)
     if bool(obj.any()):

@@ -4,7 +4,8 @@
 * its tie rule on a hand-built graph -- duplicate points and a duplicate edge: the whole gradient of a tied maximum goes to the
   lowest edge id (torch-scatter's rule, csrc/backward.hip), checked against a hand count;
 * the vectorised float64 loss (oracle/loss_oracle.py ``detection_loss_vectorised``) against the per-node restatement of the
-  trainer's loss: value and gradients to 1e-12, NaN-box and background-only batches included."""
+  trainer's loss: value and gradients to 1e-12, NaN-box and background-only batches included; Huber deltas other than 1,
+  ``ignore_index`` (-100) labels and fractional labels (tests/test_gpu_loss_edges.py uses it above a few hundred rows)."""
 import pytest
 import torch
 
@@ -226,3 +227,51 @@ def test_vectorised_loss_equals_the_per_node_oracle(n, kind):
             assert float((a - b).abs().max()) <= 1e-12 * max(1.0, float(b.abs().max())), (kind, weights)
         if kind in ("background_only", "nan_box"):
             assert float(got[2]) == 0.0 and float(got[4].abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("delta", [0.25, 1.0, 3.0])
+@pytest.mark.parametrize("weights", [None, [0.5, 2.0, 1.0, 3.0, 0.7, 0.1]])
+def test_vectorised_loss_follows_ignore_index_fractional_labels_and_delta(delta, weights):
+    """n = 300 with -100 labels (CrossEntropyLoss's ignore_index: out of the cross entropy's numerator and denominator, still an
+    object row of the box term), labels with a fraction (``.long()`` truncates toward zero: 2.7 -> 2, -0.5 -> 0, 5.999 -> 5 =
+    background) and residuals on both sides of every delta: values and gradients of the two oracles agree to 1e-12 relative."""
+    n, k, w, bg = 300, 6, 5, 5
+    g = torch.Generator().manual_seed(11)
+    cls = torch.randn(n, k, generator=g, dtype=torch.float64) * 3
+    bb = torch.randn(n, w, generator=g, dtype=torch.float64) * 2
+    label = torch.randint(0, k, (n,), generator=g).double()
+    label[::7] = -100.0
+    label[1::7] = 2.7
+    label[2::7] = -0.5
+    label[3::7] = k - 1 + 0.999
+    label[4::7] += 0.25
+    y = torch.cat([label.view(-1, 1), torch.randn(n, w, generator=g, dtype=torch.float64) * 2], 1)
+    a = (bb - y[:, 1:]).abs()
+    assert bool((a < 0.25).any()) and bool((a > 3.0).any()) and int((label == -100).sum()) > 40
+    got, exp = [], []
+    for fn, out in ((L.detection_loss_vectorised, got), (L.detection_loss, exp)):
+        c_, b_ = cls.clone().requires_grad_(True), bb.clone().requires_grad_(True)
+        loss, lc, lb = fn(c_, b_, y, bg, weights, 0.75, 2.5, delta)
+        loss.backward()
+        out += [loss.detach(), lc.detach(), lb.detach(), c_.grad, b_.grad]
+    for name, a_, b_ in zip(("loss", "loss_cls", "loss_bb", "d cls", "d bb"), got, exp):
+        assert float((a_ - b_).abs().max()) <= 1e-12 * float(b_.abs().max()), (name, delta, weights)
+    ignored = label == -100
+    assert float(exp[3][ignored].abs().max()) == 0.0 and float(got[3][ignored].abs().max()) == 0.0      # no gradient to their logits
+    assert bool((got[4][ignored].abs().sum(1) > 0).all())                                               # but they are object rows
+    background = label.long() == bg
+    assert float(got[4][background].abs().max()) == 0.0 and bool(background[3::7].all())
+    if delta != 1.0:                                                # delta reaches both oracles (it is not the default's value)
+        assert abs(float(exp[2]) - float(L.detection_loss(cls, bb, y, bg, weights, 0.75, 2.5)[2])) > 1e-3
+
+
+def test_vectorised_loss_when_every_label_is_ignored():
+    """Every label -100: 0 / 0 = NaN cross entropy in both oracles (torch's weighted mean over no row), a finite box term."""
+    g = torch.Generator().manual_seed(12)
+    cls, bb = torch.randn(40, 6, generator=g, dtype=torch.float64), torch.randn(40, 5, generator=g, dtype=torch.float64)
+    y = torch.cat([torch.full((40, 1), -100.0, dtype=torch.float64), torch.randn(40, 5, generator=g, dtype=torch.float64)], 1)
+    for weights in (None, [1.0, 1.0, 1.0, 1.0, 1.0, 0.3]):
+        a = L.detection_loss_vectorised(cls, bb, y, 5, weights)
+        b = L.detection_loss(cls, bb, y, 5, weights)
+        assert bool(torch.isnan(a[1])) and bool(torch.isnan(b[1]))
+        assert abs(float(a[2]) - float(b[2])) <= 1e-12 * float(b[2]) and float(b[2]) > 0
