@@ -1479,7 +1479,7 @@ def _win_operand_image(We: Optional[torch.Tensor], p_bias: Optional[torch.Tensor
     their cached folded weights, so the image lives exactly as long as the weights it was made from and is rebuilt when they were
     written in place or come with another bias.  None: no edge weights, or a first sight inside a stream capture (an image made there
     would belong to that graph's pool) -- the launch then builds its own image in the plan's scratch."""
-    if We is None or de == 0 or not WIN_IMAGE_CACHE:
+    if We is None or de == 0 or de > 8 or not WIN_IMAGE_CACHE:        # (de > 8: the launch itself refuses, RGNN_ERR_UNSUPPORTED)
         return None
     hit = getattr(We, "_rgnn_wplanes", None)
     if (hit is not None and hit[1] == We._version and hit[2] is p_bias and (p_bias is None or hit[3] == p_bias._version)
@@ -1501,6 +1501,8 @@ def mpnn_aggregate_win(p_bias, Q, We, ea_sorted, rowptr_t, src_sorted, plan: tor
     window of targets staged in LDS, MFMA mat-vec on exact three-term bf16 splits; de <= 8."""
     n, d = rowptr_t.numel() - 1, Q.shape[1]
     de = 0 if ea_sorted is None else ea_sorted.shape[1]
+    if ea_sorted is not None and ea_sorted.shape[0] == 0:
+        ea_sorted, We, de = None, None, 0             # a graph without edges (as in _mp_common): an empty tensor has no address
     out = padded_rows(n, d, Q.device)
     word = ctx().bounds.word() if ctx().bounds is not None else None
     tok = ctx().profiler.begin("mpnn_aggregate") if ctx().profiler is not None else None

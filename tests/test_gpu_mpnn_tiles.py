@@ -1,6 +1,7 @@
 """Window form of the max aggregation (rgnn_mpnn_aggregate_win, csrc/mpnn_tiles.hip) against a float64 evaluation of
 gnn/mpnn_layers.py:94-101 + torch-scatter max in its hoisted form, M[t] = b + max_e(Q[s_e] + W_e a_e), and against the per-edge
-kernel.  Tolerance: norm-wise 1e-5 per output tensor; the six-product bf16 split measures ~2e-7."""
+kernel.  Tolerance: norm-wise 1e-5 per output tensor; the six-product bf16 split measures ~2e-7.
+The thresholds of the plan and of both kernels on hand-built CSRs, bit-exact and element-wise: tests/test_gpu_mpnn_win_edges.py."""
 import numpy as np
 import pytest
 import torch
