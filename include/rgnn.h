@@ -430,6 +430,14 @@ int64_t rgnn_linear_planes_f16_bytes(int32_t n, int32_t k);
 int rgnn_linear_split_weights_f16(const float* W1, const float* W2, int64_t ldw, int32_t w_split, int32_t n, int32_t k,
                                   void* planes /*[dev] rgnn_linear_planes_f16_bytes(n, k) bytes*/, rgnn_stream_t stream);
 int32_t rgnn_linear_fwd_fuses_a1_affine(const rgnn_linear_args* args /*host*/);
+/* The launch plan rgnn_linear_fwd would follow for these arguments (host-side, no launch, nothing behind the pointers is read);
+ * the two queries above are views of the same plan.  out: {RGNN_LINEAR_FAMILY_*, operand form of the split-product families
+ * (RGNN_LINEAR_PATH_DMA_BF16X3 / _F16X2, else 0), columns of a tile, column tiles (both 0 on the <= 8-wide-input kernel), row-subset
+ * instance, operands through buffer descriptors, a1_scale_shift applied by the kernel (per-segment tables if a1_panel_segment
+ * is given, else one table), split-K scratch used}.  RGNN_LINEAR_FAMILY_NONE: rgnn_linear_fwd launches nothing or refuses. */
+enum { RGNN_LINEAR_FAMILY_NONE = 0, RGNN_LINEAR_FAMILY_TINY = 1, RGNN_LINEAR_FAMILY_FP32 = 2, RGNN_LINEAR_FAMILY_X3 = 3,
+       RGNN_LINEAR_FAMILY_DMA = 4 };
+void rgnn_linear_fwd_plan(const rgnn_linear_args* args /*host*/, int32_t out[8] /*host*/);
 int64_t rgnn_linear_splitk_ws_bytes(void);
 int64_t rgnn_linear_stat_panels(int64_t m);
 int32_t rgnn_linear_planes_kp(int32_t k);

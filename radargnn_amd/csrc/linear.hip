@@ -774,7 +774,7 @@ template <int BN, int WGM, int WGN, int TM, int TN, int NBUF = NBUF_DEFAULT, boo
 void launch(const LinParams& p, bool vec, bool bufl, hipStream_t s) {
   const size_t lds = (size_t)NBUF * (BM + BN) * LDK * sizeof(float);
   // persistent grid: enough workgroups to fill 256 CUs at the occupancy the LDS / register budget admits
-  int per_cu = (int)(160 * 1024 / lds) < WG_PER_CU_MAX ? (int)(160 * 1024 / lds) : WG_PER_CU_MAX;
+  int per_cu = (int)(LDS_BYTES / lds) < WG_PER_CU_MAX ? (int)(LDS_BYTES / lds) : WG_PER_CU_MAX;
   const int64_t tiles = (int64_t)p.mt * p.nt;
   int64_t grid = 256 * per_cu;
   if (grid > tiles) grid = tiles;
@@ -925,73 +925,149 @@ extern "C" int rgnn_tiny_mlp2(const float* A, int64_t lda, int32_t k0, const int
   return RGNN_OK;
 }
 
-int rgnn_linear_dma_launch(const void* lin_params, int subset, hipStream_t s);   // linear_dma.hip
-int rgnn_linear_dma_lds_bytes(int n, int64_t m, int f16_form);
+// linear_dma.hip: the LDS-DMA kernel's column-tile width (in 32-column MFMA tiles) for (n, m) and, in *lds_bytes, the LDS its
+// instance needs without the optional A1 scale / shift table; the launch of the instance plan_linear chose.
+int rgnn_linear_dma_tile(int n, int64_t m, int f16_form, int* lds_bytes);
+void rgnn_linear_dma_launch(const void* lin_params, int tn, int subset, hipStream_t s);
 
-// Does this call take the LDS-DMA bf16x3 kernel (k_linear_dma)?  One predicate for the dispatcher below and for
-// rgnn_linear_fwd_fuses_a1_affine (only that kernel applies a scale / shift to its A1 fragments).
-static bool takes_dma_kernel(const rgnn_linear_args* a) {
-  if (a == nullptr || a->m <= 0 || a->n <= 0 || a->k1 <= 0 || !a->W_planes || !a->A1 || !a->W1 || !a->out) return false;
-  if (a->k2 > 0 && !a->A2) return false;
-  if (a->w_split < a->n) return false;
-  const bool tiny = a->k2 == 0 && a->k1 <= 8 && a->n <= 64 && a->residual == nullptr && a->row_index == nullptr &&
-                    a->col_stats == nullptr && a->m >= 4096 && RGNN_ENV("RGNN_LINEAR_NO_TINY") == nullptr;
-  if (tiny) return false;
-  const bool vec = (a->k1 % 4 == 0) && (a->k2 % 4 == 0) && (a->ldw % 4 == 0) && aligned16(a->W1) &&
-                   (a->W2 == nullptr || aligned16(a->W2)) && (a->lda1 % 4 == 0 && aligned16(a->A1)) &&
-                   (a->k2 == 0 || (a->lda2 % 4 == 0 && aligned16(a->A2)));
-  const int64_t e1 = ((a->m - 1) * a->lda1 + a->k1) * 4;
+// Everything rgnn_linear_fwd decides before it launches, decided HERE and nowhere else: rgnn_linear_fwd fills LinParams from the
+// plan and switches on the family; rgnn_linear_fwd_path, rgnn_linear_fwd_fuses_a1_affine and rgnn_linear_fwd_plan report it.
+struct LinearPlan {
+  int family = RGNN_LINEAR_FAMILY_NONE;   // RGNN_LINEAR_FAMILY_* (NONE: rgnn_linear_fwd launches nothing, or refuses the arguments)
+  int form = RGNN_LINEAR_PATH_OTHER;      // operand form of the X3 / DMA families: RGNN_LINEAR_PATH_DMA_BF16X3 or _F16X2
+  bool vec = false;                       // 16-byte operand loads
+  bool bufl = false;                      // operands through buffer descriptors
+  bool direct_epilogue = false, fast_epilogue = false;
+  bool x3_subset = false;                 // X3 / DMA: the row-subset (row_index) instance
+  int ext_a1 = 0, ext_a2 = 0, ext_w = 0, ext_out = 0, ext_wp = 0;   // byte extents behind the buffer descriptors
+  int tile_cols = 0, nt = 0;              // columns of a tile, column tiles (TINY: no tiles)
+  int tn = 0;                             // FP32: 32 tn-wide tiles of the wide_tn instances (0: the 128 / 64 / 32 ladder); DMA: 32 tn
+  bool split_k = false;                   // DMA: the launch hands tiles over through splitk_ws
+  bool no_split_k = false;                // DMA: RGNN_DMA_NOPSK
+  int stagger = 100;                      // DMA: RGNN_DMA_STAGGER, per cent of the default start stagger (0: off)
+  int lds_bytes = 0;                      // DMA: LDS of the instance without the scale / shift tables
+  bool affine_batch = false;              // the kernel applies a1_scale_shift given as one whole-batch table ...
+  bool affine_segments = false;           // ... given as per-segment tables (a1_panel_segment)
+};
+
+// Pure host arithmetic on the argument VALUES: no launch, no HIP call, nothing behind a pointer is read.  Every RGNN_* switch
+// of the choice is read here, once, through RGNN_ENV (rgnn_env_reload reaches all of them together).
+static LinearPlan plan_linear(const rgnn_linear_args* a) {
+  LinearPlan pl;
+  if (a == nullptr || a->m <= 0 || a->n <= 0 || a->k1 < 0 || a->k2 < 0 || a->k1 + a->k2 <= 0 || !a->out || !a->W1 ||
+      (a->k1 > 0 && !a->A1) || (a->k2 > 0 && !a->A2) || (a->w_split < a->n && !a->W2))
+    return pl;
+  const int k = a->k1 + a->k2;
+  const bool one_w = a->w_split >= a->n;   // a single weight block: W2 is not used
+  pl.vec = (a->k1 % 4 == 0) && (a->k2 % 4 == 0) && (a->ldw % 4 == 0) && aligned16(a->W1) &&
+           (a->W2 == nullptr || aligned16(a->W2)) &&
+           (a->k1 == 0 || (a->lda1 % 4 == 0 && aligned16(a->A1))) &&
+           (a->k2 == 0 || (a->lda2 % 4 == 0 && aligned16(a->A2)));
+  // buffer-descriptor path: single weight block, extents below 2 GiB, [A1|A2] split on a k-step boundary
+  // (row_index launches pass the full row count of the matrices as m)
+  const int64_t e1 = a->k1 ? ((a->m - 1) * a->lda1 + a->k1) * 4 : 0;
   const int64_t e2 = a->k2 ? ((a->m - 1) * a->lda2 + a->k2) * 4 : 0;
-  const int64_t ew = ((int64_t)(a->n - 1) * a->ldw + a->k1 + a->k2) * 4;
+  const int64_t ew = ((int64_t)(a->n - 1) * a->ldw + k) * 4;
   const int64_t eo = ((a->m - 1) * a->ldo + a->n) * 4;
   const int64_t lim = ((int64_t)1 << 31) - 64;
-  const bool bufl = vec && e1 < lim && e2 < lim && ew < lim && (a->k2 == 0 || a->k1 % BK == 0) &&
-                    RGNN_ENV("RGNN_LINEAR_NO_BUFL") == nullptr;
-  const bool direct = a->row_index == nullptr && a->residual == nullptr && eo < lim && RGNN_ENV("RGNN_LINEAR_NO_DIRECT") == nullptr;
-  const bool x3_subset = a->row_index != nullptr && !a->accumulate && !a->gather_only && a->residual == nullptr && eo < lim &&
-                         a->relu_from_col <= 0;
-  if (!(bufl && (direct || x3_subset) && a->w_planes_kp >= a->k1 + a->k2 && a->w_planes_kp % BK == 0 &&
-        (int64_t)3 * a->n * a->w_planes_kp * 2 < lim && RGNN_ENV("RGNN_LINEAR_FP32") == nullptr))
-    return false;
-  const int dma_min_n = RGNN_ENV("RGNN_DMA_MIN_N") ? atoi(RGNN_ENV("RGNN_DMA_MIN_N")) : 32;
-  return a->n > dma_min_n && (a->k1 + a->k2) % 16 == 0 && a->k1 % 16 == 0 && RGNN_ENV("RGNN_X3_NODMA") == nullptr;
+  pl.bufl = pl.vec && a->k1 > 0 && one_w && e1 < lim && e2 < lim && ew < lim && (a->k2 == 0 || a->k1 % BK == 0) &&
+            RGNN_ENV("RGNN_LINEAR_NO_BUFL") == nullptr;
+  pl.ext_a1 = (int)e1; pl.ext_a2 = (int)e2; pl.ext_w = (int)ew; pl.ext_out = (int)(eo < lim ? eo : 0);
+  pl.fast_epilogue = (a->n % 4 == 0) && (a->ldo % 4 == 0) && aligned16(a->out) &&
+                     (a->residual == nullptr || (a->ldr % 4 == 0 && aligned16(a->residual))) &&
+                     (a->bias1 == nullptr || aligned16(a->bias1)) && (a->bias2 == nullptr || aligned16(a->bias2)) &&
+                     (one_w || a->w_split % 4 == 0);
+  pl.direct_epilogue = a->row_index == nullptr && a->residual == nullptr && eo < lim && RGNN_ENV("RGNN_LINEAR_NO_DIRECT") == nullptr;
+  const bool no_affine = RGNN_ENV("RGNN_DMA_NO_AFFINE") != nullptr;
+
+  // the <= 8-wide-input kernel: one thread per four outputs, no tiles (it clamps every column or none: relu_from_col <= 0)
+  if (a->k2 == 0 && a->k1 <= 8 && a->n <= 64 && one_w && a->residual == nullptr && a->row_index == nullptr &&
+      a->col_stats == nullptr && a->m >= 4096 && a->relu_from_col <= 0 && RGNN_ENV("RGNN_LINEAR_NO_TINY") == nullptr) {
+    pl.family = RGNN_LINEAR_FAMILY_TINY;
+    return pl;
+  }
+
+  // the split-product kernels (k_linear_x3, k_linear_dma): pre-split weight planes supplied, buffer-descriptor operands, and an
+  // epilogue that stores straight from the accumulators -- direct, or on a row list (which clamps every column or none)
+  const bool subset = a->row_index != nullptr && !a->accumulate && !a->gather_only && a->residual == nullptr && eo < lim &&
+                      a->relu_from_col <= 0;
+  if (a->W_planes && pl.bufl && (pl.direct_epilogue || subset) && a->w_planes_kp >= k && a->w_planes_kp % BK == 0 &&
+      (int64_t)3 * a->n * a->w_planes_kp * 2 < lim && RGNN_ENV("RGNN_LINEAR_FP32") == nullptr) {
+    pl.x3_subset = subset;
+    pl.form = RGNN_LINEAR_PATH_DMA_BF16X3;
+    pl.ext_wp = (int)((int64_t)3 * a->n * a->w_planes_kp * 2);
+    // LDS-DMA staged kernel (linear_dma.hip): wide layers whose reduction splits into whole k-steps of 16
+    // (32 < n <= 64, e.g. the last conv layer's update: few MFMAs per k-step, the kernel then runs at the rate its
+    // activation stream arrives -- still ahead of the fp32-MFMA kernel the narrow layers used to take)
+    const int dma_min_n = RGNN_ENV("RGNN_DMA_MIN_N") ? atoi(RGNN_ENV("RGNN_DMA_MIN_N")) : 32;
+    if (a->n > dma_min_n && k % 16 == 0 && a->k1 % 16 == 0 && RGNN_ENV("RGNN_X3_NODMA") == nullptr) {
+      pl.family = RGNN_LINEAR_FAMILY_DMA;
+      // f16x2 form (two f16 terms per operand, three products): f16 planes (+ footer) and the bounds of both activation blocks given
+      if (a->W_planes_f16 != nullptr && a->a1_bound != nullptr && (a->k2 == 0 || a->a2_bound != nullptr) &&
+          RGNN_ENV("RGNN_LINEAR_NO_F16") == nullptr) {
+        pl.form = RGNN_LINEAR_PATH_DMA_F16X2;
+        pl.ext_wp = (int)((int64_t)2 * a->n * a->w_planes_kp * 2);
+      }
+      pl.tn = rgnn_linear_dma_tile(a->n, a->m, pl.form == RGNN_LINEAR_PATH_DMA_F16X2, &pl.lds_bytes);
+      pl.tile_cols = 32 * pl.tn; pl.nt = (a->n + pl.tile_cols - 1) / pl.tile_cols;
+      pl.split_k = a->splitk_ws && a->splitk_ws_bytes >= rgnn_linear_splitk_ws_bytes() && RGNN_ENV("RGNN_DMA_NOSK") == nullptr;
+      pl.no_split_k = RGNN_ENV("RGNN_DMA_NOPSK") != nullptr;
+      pl.stagger = RGNN_ENV("RGNN_DMA_STAGGER") ? atoi(RGNN_ENV("RGNN_DMA_STAGGER")) : 100;
+      // the scale / shift tables live in LDS next to the tiles: one table, or two resident ones for a segmented row list
+      const int64_t table = RGNN_AFFINE_ROWS * 4 * (int64_t)a->k1;
+      pl.affine_batch = !no_affine && pl.lds_bytes + table <= LDS_BYTES;
+      pl.affine_segments = !no_affine && subset && a->k1 <= 512 && pl.lds_bytes + 2 * table <= LDS_BYTES;
+      return pl;
+    }
+    pl.family = RGNN_LINEAR_FAMILY_X3;
+    // 256 x 256 tiles (k-step 16) move 28 % fewer operand bytes per flop than 256 x 128 (k-step 32) and measure 5 - 15 %
+    // faster, unless they pad more columns (N = 272: 512 against 384)
+    const int pad_w = (a->n + 255) / 256 * 256, pad_n = (a->n + 127) / 128 * 128;
+    const bool wide = a->n > 128 && pad_w * 100 <= pad_n * 107 && RGNN_ENV("RGNN_X3_NARROW") == nullptr;
+    pl.tile_cols = wide ? 256 : a->n > 64 ? 128 : a->n > 32 ? 64 : 32;
+    pl.nt = (a->n + pl.tile_cols - 1) / pl.tile_cols;
+    return pl;
+  }
+
+  pl.family = RGNN_LINEAR_FAMILY_FP32;
+  // column tiling: 32*TN-wide tiles (4 waves stacked in M, each 32 x 32*TN) when that wastes fewer padded columns
+  // than 128-wide tiles -- N = 224 -> one 224 tile (0 % instead of 12.5 % padding), 464 -> 3 x 160, 928 -> 6 x 160
+  // (measured, M = 192k: N = 464 / K = 224 +5 %, N = 224 / K = 688 +4 %; not worth it for short reductions or N > 512)
+  if (pl.bufl && a->row_index == nullptr && a->n > 128 && a->n <= 512 && k >= 192) {
+    const int base = ((a->n + 127) / 128) * 128;
+    int best = base;
+    for (int tn = 3; tn <= 7; tn++) {
+      const int w = 32 * tn, padded = ((a->n + w - 1) / w) * w;
+      if (padded < best || (padded == best && pl.tn)) { best = padded; pl.tn = tn; }
+    }
+    if (best * 100 > base * 95) pl.tn = 0;  // needs >= 5 % fewer padded columns
+  }
+  pl.tile_cols = pl.tn ? 32 * pl.tn : a->n > 64 ? 128 : a->n > 32 ? 64 : 32;
+  pl.nt = (a->n + pl.tile_cols - 1) / pl.tile_cols;
+  // k_linear applies the table on its buffer-descriptor path.  CONSERVATIVE ON PURPOSE: a call that carries weight planes and
+  // still lands here (RGNN_LINEAR_FP32, planes too narrow, an epilogue the split-product kernels lack) is reported as NOT
+  // fusing, so its caller keeps the separate rgnn_scale_shift_act pass -- the launch sequence of bench.py's fp32 line.
+  const bool planes_keep_separate_pass = a->W_planes != nullptr;
+  pl.affine_batch = !no_affine && pl.bufl && !planes_keep_separate_pass;
+  return pl;
 }
 
-// ... or the fp32-MFMA kernel with buffer-descriptor operands (k_linear<..., BUFL = true>: the narrow layers, no weight planes)?
-static bool takes_fp32_bufl_kernel(const rgnn_linear_args* a) {
-  if (a == nullptr || a->m <= 0 || a->n <= 0 || a->k1 <= 0 || a->W_planes || !a->A1 || !a->W1 || !a->out) return false;
-  if (a->k2 > 0 && !a->A2) return false;
-  if (a->w_split < a->n) return false;
-  const bool tiny = a->k2 == 0 && a->k1 <= 8 && a->n <= 64 && a->residual == nullptr && a->row_index == nullptr &&
-                    a->col_stats == nullptr && a->m >= 4096 && a->relu_from_col <= 0 && RGNN_ENV("RGNN_LINEAR_NO_TINY") == nullptr;
-  if (tiny) return false;
-  const bool vec = (a->k1 % 4 == 0) && (a->k2 % 4 == 0) && (a->ldw % 4 == 0) && aligned16(a->W1) &&
-                   (a->lda1 % 4 == 0 && aligned16(a->A1)) && (a->k2 == 0 || (a->lda2 % 4 == 0 && aligned16(a->A2)));
-  const int64_t e1 = ((a->m - 1) * a->lda1 + a->k1) * 4;
-  const int64_t e2 = a->k2 ? ((a->m - 1) * a->lda2 + a->k2) * 4 : 0;
-  const int64_t ew = ((int64_t)(a->n - 1) * a->ldw + a->k1 + a->k2) * 4;
-  const int64_t lim = ((int64_t)1 << 31) - 64;
-  return vec && e1 < lim && e2 < lim && ew < lim && (a->k2 == 0 || a->k1 % BK == 0) && RGNN_ENV("RGNN_LINEAR_NO_BUFL") == nullptr;
-}
-
-// ... and in its f16x2 form (two f16 terms per operand, three products): f16 planes + bounds of both activation blocks given
-static bool takes_f16_form(const rgnn_linear_args* a) {
-  return a->W_planes_f16 != nullptr && a->a1_bound != nullptr && (a->k2 == 0 || a->a2_bound != nullptr) &&
-         RGNN_ENV("RGNN_LINEAR_NO_F16") == nullptr;
-}
 extern "C" int32_t rgnn_linear_fwd_path(const rgnn_linear_args* a) {
-  if (!takes_dma_kernel(a)) return RGNN_LINEAR_PATH_OTHER;
-  return takes_f16_form(a) ? RGNN_LINEAR_PATH_DMA_F16X2 : RGNN_LINEAR_PATH_DMA_BF16X3;
+  const LinearPlan pl = plan_linear(a);
+  return pl.family == RGNN_LINEAR_FAMILY_DMA ? pl.form : RGNN_LINEAR_PATH_OTHER;
 }
 
+static bool applies_a1_affine(const LinearPlan& pl, const rgnn_linear_args* a) {
+  return a->a1_panel_segment != nullptr ? pl.affine_segments : pl.affine_batch;
+}
 extern "C" int32_t rgnn_linear_fwd_fuses_a1_affine(const rgnn_linear_args* a) {
-  if (RGNN_ENV("RGNN_DMA_NO_AFFINE") != nullptr) return 0;
-  if (a->a1_panel_segment != nullptr)           // per-segment tables: the LDS-DMA kernel on a row list, two tables resident
-    return (a->row_index != nullptr && takes_dma_kernel(a) && a->k1 <= 512 &&
-            rgnn_linear_dma_lds_bytes(a->n, a->m, takes_f16_form(a)) + 2 * RGNN_AFFINE_ROWS * 4 * (int64_t)a->k1 <= 160 * 1024) ? 1 : 0;
-  if (takes_fp32_bufl_kernel(a)) return 1;
-  if (!takes_dma_kernel(a)) return 0;
-  return rgnn_linear_dma_lds_bytes(a->n, a->m, takes_f16_form(a)) + RGNN_AFFINE_ROWS * 4 * (int64_t)a->k1 <= 160 * 1024 ? 1 : 0;
+  return a != nullptr && applies_a1_affine(plan_linear(a), a) ? 1 : 0;
+}
+
+extern "C" void rgnn_linear_fwd_plan(const rgnn_linear_args* a, int32_t out[8]) {
+  const LinearPlan pl = plan_linear(a);
+  out[0] = pl.family; out[1] = pl.form; out[2] = pl.tile_cols; out[3] = pl.nt;
+  out[4] = pl.x3_subset; out[5] = pl.bufl; out[6] = a != nullptr && applies_a1_affine(pl, a); out[7] = pl.split_k;
 }
 
 extern "C" int64_t rgnn_linear_stat_panels(int64_t m) { return (m + BM - 1) / BM; }
@@ -1006,154 +1082,75 @@ extern "C" int rgnn_linear_fwd(const rgnn_linear_args* a, rgnn_stream_t stream) 
   RGNN_CHECK_ARG(a->out && a->W1 && (a->k1 == 0 || a->A1) && (a->k2 == 0 || a->A2), "null pointers");
   RGNN_CHECK_ARG(a->w_split >= a->n || a->W2, "w_split < n needs W2");
   RGNN_CHECK_ARG(a->m < ((int64_t)1 << 31) * BM, "m too large");
-  LinParams p;
-  p.sk_ws = nullptr; p.sk_flags = nullptr; p.no_split_k = RGNN_ENV("RGNN_DMA_NOPSK") != nullptr;
-  { static const int stg = RGNN_ENV("RGNN_DMA_STAGGER") ? atoi(RGNN_ENV("RGNN_DMA_STAGGER")) : 100; p.stagger = stg; }   // per cent of the default start stagger (0: off)
-  p.a1_aff = a->a1_scale_shift; p.a1_relu = a->a1_relu; p.a1_aff_panel = a->a1_panel_segment;
   RGNN_CHECK_ARG(a->a1_panel_segment == nullptr || a->a1_scale_shift != nullptr, "a1_panel_segment needs a1_scale_shift");
-  p.relu_lo = a->relu_from_col > 0 ? a->relu_from_col : 0;
-  p.fmt = 0; p.a1_bound = a->a1_bound; p.a2_bound = a->a2_bound; p.out_absmax = a->out_absmax;
-  if (a->out_absmax != nullptr && !takes_dma_kernel(a)) {
+  const LinearPlan pl = plan_linear(a);
+  if (a->out_absmax != nullptr && pl.family != RGNN_LINEAR_FAMILY_DMA) {
     rgnn_set_error("rgnn_linear_fwd: out_absmax needs the LDS-DMA kernel (rgnn_linear_fwd_path != 0)");
     return RGNN_ERR_UNSUPPORTED;
   }
-  if (a->a1_scale_shift != nullptr && !rgnn_linear_fwd_fuses_a1_affine(a)) {
+  if (a->a1_scale_shift != nullptr && !applies_a1_affine(pl, a)) {
     rgnn_set_error("rgnn_linear_fwd: a1_scale_shift needs the LDS-DMA kernel (rgnn_linear_fwd_fuses_a1_affine): apply "
                    "rgnn_scale_shift_act to A1 instead");
     return RGNN_ERR_UNSUPPORTED;
   }
-  p.A1 = a->A1; p.A2 = a->A2; p.lda1 = a->lda1; p.lda2 = a->lda2; p.k1 = a->k1; p.k2 = a->k2;
-  p.W1 = a->W1; p.W2 = a->W2; p.ldw = a->ldw; p.w_split = a->w_split >= a->n ? a->n : a->w_split;
-  p.bias1 = a->bias1; p.bias2 = a->bias2;
-  p.residual = a->residual; p.ldr = a->ldr;
-  p.out = a->out; p.ldo = a->ldo; p.m = a->m; p.n = a->n; p.relu_out = a->relu_out; p.col_stats = a->col_stats;
-  p.row_index = a->row_index; p.m_dev = a->m_dev; p.accumulate = a->accumulate;
-  p.gather_only = a->gather_only; p.res_index = a->residual_index;
   RGNN_CHECK_ARG(a->row_index != nullptr || (a->m_dev == nullptr && a->accumulate == 0), "m_dev / accumulate need row_index");
   RGNN_CHECK_ARG(!(a->accumulate && a->col_stats), "col_stats of an accumulating launch are not defined (statistics are sums about a pivot of the stored values)");
-  p.mt = (int)((a->m + BM - 1) / BM);
-  const bool vec = (a->k1 % 4 == 0) && (a->k2 % 4 == 0) && (a->ldw % 4 == 0) && aligned16(a->W1) &&
-                   (a->W2 == nullptr || aligned16(a->W2)) &&
-                   (a->k1 == 0 || (a->lda1 % 4 == 0 && aligned16(a->A1))) &&
-                   (a->k2 == 0 || (a->lda2 % 4 == 0 && aligned16(a->A2)));
-  // buffer-descriptor path: single weight block, extents below 2 GiB, [A1|A2] split on a k-step boundary
-  const int64_t rows_a = a->m;  // row_index launches pass the full row count of the matrices as m
-  const int64_t e1 = a->k1 ? ((rows_a - 1) * a->lda1 + a->k1) * 4 : 0;
-  const int64_t e2 = a->k2 ? ((rows_a - 1) * a->lda2 + a->k2) * 4 : 0;
-  const int64_t ew = ((int64_t)(a->n - 1) * a->ldw + a->k1 + a->k2) * 4;
-  const int64_t lim = ((int64_t)1 << 31) - 64;
-  const bool bufl = vec && a->k1 > 0 && (a->w_split >= a->n) && e1 < lim && e2 < lim && ew < lim &&
-                    (a->k2 == 0 || a->k1 % BK == 0) && RGNN_ENV("RGNN_LINEAR_NO_BUFL") == nullptr;
-  p.ext_a1 = (int)e1; p.ext_a2 = (int)e2; p.ext_w = (int)ew;
-  p.fast_epilogue = (a->n % 4 == 0) && (a->ldo % 4 == 0) && aligned16(a->out) &&
-                    (a->residual == nullptr || (a->ldr % 4 == 0 && aligned16(a->residual))) &&
-                    (a->bias1 == nullptr || aligned16(a->bias1)) && (a->bias2 == nullptr || aligned16(a->bias2)) &&
-                    (a->w_split >= a->n || a->w_split % 4 == 0);
-  const int64_t eo = ((a->m - 1) * a->ldo + a->n) * 4;
-  p.direct_epilogue = a->row_index == nullptr && a->residual == nullptr && eo < lim && RGNN_ENV("RGNN_LINEAR_NO_DIRECT") == nullptr;
-  p.ext_out = (int)(eo < lim ? eo : 0);
   hipStream_t s = (hipStream_t)stream;
-  if (a->k2 == 0 && a->k1 <= 8 && a->n <= 64 && a->w_split >= a->n && a->residual == nullptr && a->row_index == nullptr &&
-      a->col_stats == nullptr && a->m >= 4096 && a->relu_from_col <= 0 && RGNN_ENV("RGNN_LINEAR_NO_TINY") == nullptr) {
+  if (pl.family == RGNN_LINEAR_FAMILY_TINY) {
     const bool v4 = (a->n % 4 == 0) && (a->ldo % 4 == 0) && aligned16(a->out);
     const int64_t threads = a->m * ((a->n + 3) / 4);
     const int64_t tiny_blocks = rgnn_blocks(threads, 256) < 4096 ? rgnn_blocks(threads, 256) : 4096;
     rgnn_prof_begin(s);
-    if (v4)
-      hipLaunchKernelGGL(k_linear_tiny<true>, dim3((unsigned)tiny_blocks), dim3(256), 0, s, (const float*)a->A1, a->lda1,
-                         a->k1, (const float*)a->W1, a->ldw, (const float*)a->bias1, a->m, a->n, a->relu_out, (float*)a->out, a->ldo);
-    else
-      hipLaunchKernelGGL(k_linear_tiny<false>, dim3((unsigned)tiny_blocks), dim3(256), 0, s, (const float*)a->A1, a->lda1,
-                         a->k1, (const float*)a->W1, a->ldw, (const float*)a->bias1, a->m, a->n, a->relu_out, (float*)a->out, a->ldo);
+    hipLaunchKernelGGL(v4 ? k_linear_tiny<true> : k_linear_tiny<false>, dim3((unsigned)tiny_blocks), dim3(256), 0, s, (const float*)a->A1,
+                       a->lda1, a->k1, (const float*)a->W1, a->ldw, (const float*)a->bias1, a->m, a->n, a->relu_out, (float*)a->out, a->ldo);
     rgnn_prof_end(s);
     RGNN_CHECK_LAUNCH();
     return RGNN_OK;
   }
-  // bf16x3 path (see k_linear_x3): pre-split weight planes supplied, buffer-descriptor operands, direct epilogue
-  p.Wp = a->W_planes; p.kp = a->w_planes_kp;
-  p.ext_wp = 0;
-  const bool x3_subset = a->row_index != nullptr && !a->accumulate && !a->gather_only && a->residual == nullptr && eo < lim &&
-                         a->relu_from_col <= 0;   // (the row-subset epilogue clamps every column or none)
-  if (a->W_planes && bufl && (p.direct_epilogue || x3_subset) && a->w_planes_kp >= a->k1 + a->k2 && a->w_planes_kp % BK == 0 &&
-      (int64_t)3 * a->n * a->w_planes_kp * 2 < lim && RGNN_ENV("RGNN_LINEAR_FP32") == nullptr) {
-    p.ext_wp = (int)((int64_t)3 * a->n * a->w_planes_kp * 2);
-    rgnn_prof_begin(s);
-    // LDS-DMA staged kernel (linear_dma.hip): wide layers whose reduction splits into whole k-steps of 16
-    // (32 < n <= 64, e.g. the last conv layer's update: few MFMAs per k-step, the kernel then runs at the rate its
-    // activation stream arrives -- still ahead of the fp32-MFMA kernel the narrow layers used to take)
-    static const int dma_min_n = RGNN_ENV("RGNN_DMA_MIN_N") ? atoi(RGNN_ENV("RGNN_DMA_MIN_N")) : 32;
-    if (a->n > dma_min_n && (a->k1 + a->k2) % 16 == 0 && a->k1 % 16 == 0 && RGNN_ENV("RGNN_X3_NODMA") == nullptr) {
-      if (a->splitk_ws && a->splitk_ws_bytes >= rgnn_linear_splitk_ws_bytes() && RGNN_ENV("RGNN_DMA_NOSK") == nullptr) {
-        p.sk_ws = a->splitk_ws;
-        p.sk_flags = (int*)((char*)a->splitk_ws + (int64_t)256 * 8 * 16 * 512 * 4);
-      }
-      if (takes_f16_form(a)) {                          // two f16 planes (+ footer) instead of three bf16 planes
-        p.fmt = 1; p.Wp = a->W_planes_f16;
-        p.ext_wp = (int)((int64_t)2 * a->n * a->w_planes_kp * 2);
-      }
-      const int rc_dma = rgnn_linear_dma_launch(&p, x3_subset ? 1 : 0, s);
-      rgnn_prof_end(s);
-      if (rc_dma != RGNN_OK) return rc_dma;
-      RGNN_CHECK_LAUNCH();
-      return RGNN_OK;
-    }
-    if (a->a1_scale_shift != nullptr) {               // (takes_dma_kernel and this dispatcher must agree)
-      rgnn_set_error("rgnn_linear_fwd: internal: a1_scale_shift accepted but the LDS-DMA kernel was not selected");
-      return RGNN_ERR_UNSUPPORTED;
-    }
-    // 256 x 256 tiles (k-step 16) move 28 % fewer operand bytes per flop than 256 x 128 (k-step 32) and measure 5 - 15 %
-    // faster, unless they pad more columns (N = 272: 512 against 384)
-    const int pad_w = (a->n + 255) / 256 * 256, pad_n = (a->n + 127) / 128 * 128;
-    const bool wide = a->n > 128 && pad_w * 100 <= pad_n * 107 && RGNN_ENV("RGNN_X3_NARROW") == nullptr;
-#define RGNN_X3(IDX)                                                                                    \
-  do {                                                                                                  \
-    if (wide) { p.nt = (a->n + 255) / 256; launch_x3<IDX, 256, 256, 2, 4, 4, 2, 16, 1>(p, s); }        \
-    else if (a->n > 64) { p.nt = (a->n + 127) / 128; launch_x3<IDX, 256, 128, 4, 2, 2, 2>(p, s); }     \
-    else if (a->n > 32) { p.nt = 1; launch_x3<IDX, 256, 64, 4, 2, 2, 1>(p, s); }                       \
-    else { p.nt = 1; launch_x3<IDX, 256, 32, 8, 1, 1, 1>(p, s); }                                      \
-  } while (0)
-    if (x3_subset) RGNN_X3(true); else RGNN_X3(false);
-#undef RGNN_X3
-    rgnn_prof_end(s);
-    RGNN_CHECK_LAUNCH();
-    return RGNN_OK;
-  }
-  if (a->a1_scale_shift != nullptr && !bufl) {        // (the fp32 kernel applies it on its buffer-descriptor path only)
-    rgnn_set_error("rgnn_linear_fwd: internal: a1_scale_shift accepted but no kernel that applies it was selected");
-    return RGNN_ERR_UNSUPPORTED;
-  }
+  const bool f16 = pl.family == RGNN_LINEAR_FAMILY_DMA && pl.form == RGNN_LINEAR_PATH_DMA_F16X2;
+  LinParams p;
+  p.A1 = a->A1; p.A2 = a->A2; p.lda1 = a->lda1; p.lda2 = a->lda2; p.k1 = a->k1; p.k2 = a->k2;
+  p.W1 = a->W1; p.W2 = a->W2; p.ldw = a->ldw; p.w_split = a->w_split >= a->n ? a->n : a->w_split;
+  p.bias1 = a->bias1; p.bias2 = a->bias2; p.residual = a->residual; p.ldr = a->ldr;
+  p.out = a->out; p.ldo = a->ldo; p.m = a->m; p.n = a->n; p.relu_out = a->relu_out; p.col_stats = a->col_stats;
+  p.mt = (int)((a->m + BM - 1) / BM); p.nt = pl.nt;
+  p.ext_a1 = pl.ext_a1; p.ext_a2 = pl.ext_a2; p.ext_w = pl.ext_w;
+  p.row_index = a->row_index; p.m_dev = a->m_dev; p.gather_only = a->gather_only; p.res_index = a->residual_index; p.accumulate = a->accumulate;
+  p.fast_epilogue = pl.fast_epilogue; p.direct_epilogue = pl.direct_epilogue; p.ext_out = pl.ext_out;
+  p.Wp = f16 ? a->W_planes_f16 : a->W_planes; p.kp = a->w_planes_kp; p.ext_wp = pl.ext_wp;
+  p.sk_ws = pl.split_k ? a->splitk_ws : nullptr;
+  p.sk_flags = pl.split_k ? (int*)((char*)a->splitk_ws + (int64_t)256 * 8 * 16 * 512 * 4) : nullptr;
+  p.no_split_k = pl.no_split_k; p.stagger = pl.stagger;
+  p.a1_aff = a->a1_scale_shift; p.a1_relu = a->a1_relu; p.a1_aff_panel = a->a1_panel_segment;
+  p.relu_lo = a->relu_from_col > 0 ? a->relu_from_col : 0;
+  p.fmt = f16 ? 1 : 0; p.a1_bound = a->a1_bound; p.a2_bound = a->a2_bound; p.out_absmax = a->out_absmax;
   rgnn_prof_begin(s);
-  // column tiling: 32*TN-wide tiles (4 waves stacked in M, each 32 x 32*TN) when that wastes fewer padded columns
-  // than 128-wide tiles -- N = 224 -> one 224 tile (0 % instead of 12.5 % padding), 464 -> 3 x 160, 928 -> 6 x 160
-  int wide_tn = 0;
-  // (measured, M = 192k: N = 464 / K = 224 +5 %, N = 224 / K = 688 +4 %; not worth it for short reductions or N > 512)
-  if (bufl && a->row_index == nullptr && a->n > 128 && a->n <= 512 && a->k1 + a->k2 >= 192) {
-    const int base = ((a->n + 127) / 128) * 128;
-    int best = base;
-    for (int tn = 3; tn <= 7; tn++) {
-      const int w = 32 * tn, padded = ((a->n + w - 1) / w) * w;
-      if (padded < best || (padded == best && wide_tn)) { best = padded; wide_tn = tn; }
+  if (pl.family == RGNN_LINEAR_FAMILY_DMA) {
+    rgnn_linear_dma_launch(&p, pl.tn, pl.x3_subset, s);
+  } else if (pl.family == RGNN_LINEAR_FAMILY_X3) {
+#define RGNN_X3(IDX)                                                                         \
+  do {                                                                                       \
+    if (pl.tile_cols == 256) launch_x3<IDX, 256, 256, 2, 4, 4, 2, 16, 1>(p, s);              \
+    else if (pl.tile_cols == 128) launch_x3<IDX, 256, 128, 4, 2, 2, 2>(p, s);                \
+    else if (pl.tile_cols == 64) launch_x3<IDX, 256, 64, 4, 2, 2, 1>(p, s);                  \
+    else launch_x3<IDX, 256, 32, 8, 1, 1, 1>(p, s);                                          \
+  } while (0)
+    if (pl.x3_subset) RGNN_X3(true); else RGNN_X3(false);
+#undef RGNN_X3
+  } else if (pl.tn) {
+    switch (pl.tn) {
+      case 3: launch<96, 4, 1, 1, 3, 1, true>(p, pl.vec, pl.bufl, s); break;
+      case 4: launch<128, 4, 1, 1, 4, 1, true>(p, pl.vec, pl.bufl, s); break;
+      case 5: launch<160, 4, 1, 1, 5, 1, true>(p, pl.vec, pl.bufl, s); break;
+      case 6: launch<192, 4, 1, 1, 6, 1, true>(p, pl.vec, pl.bufl, s); break;
+      default: launch<224, 4, 1, 1, 7, 1, true>(p, pl.vec, pl.bufl, s); break;
     }
-    if (best * 100 > base * 95) wide_tn = 0;  // needs >= 5 % fewer padded columns
-  }
-  if (wide_tn) {
-    p.nt = (a->n + 32 * wide_tn - 1) / (32 * wide_tn);
-    switch (wide_tn) {
-      case 3: launch<96, 4, 1, 1, 3, 1, true>(p, vec, bufl, s); break;
-      case 4: launch<128, 4, 1, 1, 4, 1, true>(p, vec, bufl, s); break;
-      case 5: launch<160, 4, 1, 1, 5, 1, true>(p, vec, bufl, s); break;
-      case 6: launch<192, 4, 1, 1, 6, 1, true>(p, vec, bufl, s); break;
-      default: launch<224, 4, 1, 1, 7, 1, true>(p, vec, bufl, s); break;
-    }
-  } else if (a->n > 64) {
-    p.nt = (a->n + 127) / 128;
-    launch<128, 2, 2, 2, 2>(p, vec, bufl, s);   // 4 waves of 64x64
-  } else if (a->n > 32) {
-    p.nt = 1;
-    launch<64, 2, 2, 2, 1>(p, vec, bufl, s);
+  } else if (pl.tile_cols == 128) {
+    launch<128, 2, 2, 2, 2>(p, pl.vec, pl.bufl, s);   // 4 waves of 64x64
+  } else if (pl.tile_cols == 64) {
+    launch<64, 2, 2, 2, 1>(p, pl.vec, pl.bufl, s);
   } else {
-    p.nt = 1;
-    launch<32, 4, 1, 1, 1>(p, vec, bufl, s);
+    launch<32, 4, 1, 1, 1>(p, pl.vec, pl.bufl, s);
   }
   rgnn_prof_end(s);
   RGNN_CHECK_LAUNCH();

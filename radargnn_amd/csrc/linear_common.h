@@ -31,6 +31,7 @@ __device__ __forceinline__ void bound_raise(float* __restrict__ b, int slot, flo
 constexpr int BM = RGNN_STAT_PANEL_ROWS;   // (also the height of a column-statistics panel)
 constexpr int BK = 32;
 constexpr int LDK = 36;
+constexpr int LDS_BYTES = 160 * 1024;   // LDS of a CU: what one work-group can have, tiles and scale / shift tables together
 
 struct LinParams {
   const float* A1; const float* A2; int64_t lda1, lda2; int k1, k2;

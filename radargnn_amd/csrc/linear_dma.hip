@@ -742,7 +742,7 @@ void launch_dma(LinParams p, hipStream_t s) {
   grid = (grid + 7) / 8 * 8;
   static RgnnOncePerDevice attr_once;
   if (attr_once.first()) {                                  // (room for the optional scale / shift table of the A1 operand: up to 1 024 columns)
-    const int most = dma_lds_bytes(BN, NPL, WV) + 12288 < 160 * 1024 ? dma_lds_bytes(BN, NPL, WV) + 12288 : 160 * 1024;
+    const int most = dma_lds_bytes(BN, NPL, WV) + 12288 < LDS_BYTES ? dma_lds_bytes(BN, NPL, WV) + 12288 : LDS_BYTES;
     hipFuncSetAttribute((const void*)k_linear_dma<TN, IDX, FMT, WV>, hipFuncAttributeMaxDynamicSharedMemorySize, most);
   }
   hipLaunchKernelGGL((k_linear_dma<TN, IDX, FMT, WV>), dim3((unsigned)grid), dim3(DMA_THREADS), lds, s, p);
@@ -793,18 +793,21 @@ static bool dma_four_waves(const LinParams& p, int tn, int waves_env) {
   return false;
 }
 
-// LDS bytes the kernel instance for (n, m) needs without the optional A1 scale / shift table (linear.hip: does the table fit?)
+// What plan_linear (linear.hip) asks once per launch: the column-tile width for (n, m), and in *lds_bytes the LDS that kernel
+// instance needs without the optional A1 scale / shift tables (does a table fit next to the tiles?)
 // (f16_form: the launch carries f16 weight planes and bounds -- the f16x2 form's weight stages are smaller than the bf16x3 form's)
-int rgnn_linear_dma_lds_bytes(int n, int64_t m, int f16_form) {
+int rgnn_linear_dma_tile(int n, int64_t m, int f16_form, int* lds_bytes) {
   const int npl = f16_form ? 2 : 3;
-  return dma_lds_bytes(32 * dma_pick_tn(n, m, npl), npl);
+  const int tn = dma_pick_tn(n, m, npl);
+  *lds_bytes = dma_lds_bytes(32 * tn, npl);
+  return tn;
 }
 
-// Called by rgnn_linear_fwd (linear.hip) once it has decided that the layer qualifies (bf16 planes given, buffer-descriptor
-// operands, n > 64, K and k1 multiples of 16, no residual / accumulate / gather_only).  `subset`: row_index launch.
-int rgnn_linear_dma_launch(const void* params, int subset, hipStream_t s) {
+// Called by rgnn_linear_fwd (linear.hip) once plan_linear has decided that the layer qualifies (bf16 planes given, buffer-descriptor
+// operands, n > 32, K and k1 multiples of 16, no residual / accumulate / gather_only) and which tile width `tn` it takes.
+// `subset`: row_index launch.
+void rgnn_linear_dma_launch(const void* params, int tn, int subset, hipStream_t s) {
   const LinParams& p = *(const LinParams*)params;
-  const int tn = dma_pick_tn(p.n, p.m, p.fmt == 1 ? 2 : 3);
   // two 4-wave work-groups per CU instead of one of eight (f16x2 form): RGNN_DMA_WAVES = 4 forces it, 8 forbids it
   const char* waves_e = RGNN_ENV("RGNN_DMA_WAVES");          // (read per call: tools/x3_bench switches it between variants)
   const int waves_env = waves_e ? atoi(waves_e) : 0;
@@ -823,5 +826,4 @@ int rgnn_linear_dma_launch(const void* params, int subset, hipStream_t s) {
       else { if (subset) launch_dma<8, true, 0>(p, s); else launch_dma<8, false, 0>(p, s); }
   }
 #undef RGNN_DMA
-  return 0;
 }

@@ -1041,16 +1041,19 @@ def linear(a1: torch.Tensor, w1: torch.Tensor, bias1: Optional[torch.Tensor] = N
                               _ptr(aff), 1 if a1_relu else 0, int(relu_from), None, None, None, None,
                               _ptr(a1_affine_tiles) if aff is not None else None)
 
-    def add_f16(args_) -> bool:
-        """Fill in the f16x2 operands when the launch can take that form -- BEFORE asking whether the BatchNorm-apply fits the
-        kernel's LDS next to its tiles: the two forms have different budgets (rgnn_linear_fwd_fuses_a1_affine)."""
-        if (track and USE_F16X2 and b1 is not None and (a2 is None or b2 is not None)
-                and lib.rgnn_linear_fwd_path(C.byref(args_)) != 0):
+    def prepare(a1_, aff):
+        """The arguments of the launch, whether the LDS-DMA kernel takes it, and whether in its f16x2 form.  The library is asked
+        ONCE per argument set (the kernel family does not depend on the f16 operands), and the f16x2 operands are filled in
+        BEFORE anyone asks whether the BatchNorm-apply fits the kernel's LDS next to its tiles: the two forms have different
+        budgets (rgnn_linear_fwd_fuses_a1_affine)."""
+        args_ = make_args(a1_, aff)
+        dma_ = lib.rgnn_linear_fwd_path(C.byref(args_)) != 0
+        f16_ = bool(dma_ and track and USE_F16X2 and b1 is not None and (a2 is None or b2 is not None))
+        if f16_:
             planes16 = weight_planes_f16(w1, w2, k1 + k2, cache_planes)
             args_.W_planes_f16, args_.a1_bound, args_.a2_bound = _ptr(planes16), _ptr(b1), _ptr(b2)
             args_._keep = planes16
-            return True
-        return False
+        return args_, dma_, f16_
 
     if a1_affine_tiles is not None:
         # per-segment tables [S, AFFINE_ROWS, k1] (frames normalised with their own statistics): ``row_index`` is a list padded per segment
@@ -1062,8 +1065,7 @@ def linear(a1: torch.Tensor, w1: torch.Tensor, bias1: Optional[torch.Tensor] = N
         _dev(a1_affine_tiles, "a1_affine_tiles", torch.int32)
         if a1_affine.dim() != 3 or a1_affine.shape[1:] != (AFFINE_ROWS, k1):
             raise ValueError("a1_affine must be [S, AFFINE_ROWS, k1] with a1_affine_tiles")
-        args = make_args(a1, a1_affine)
-        f16 = add_f16(args)
+        args, dma, f16 = prepare(a1, a1_affine)
         if not lib.rgnn_linear_fwd_fuses_a1_affine(C.byref(args)):
             raise RgnnError("this launch cannot apply per-segment scale / shift tables (not on the LDS-DMA kernel)")
         COUNTERS["fused_a1_affine_segments"] = COUNTERS.get("fused_a1_affine_segments", 0) + 1
@@ -1071,25 +1073,22 @@ def linear(a1: torch.Tensor, w1: torch.Tensor, bias1: Optional[torch.Tensor] = N
         a1_affine = _dev(a1_affine, "a1_affine", torch.float32).contiguous()
         if a1_affine.shape != (AFFINE_ROWS, k1):
             raise ValueError("a1_affine must be [AFFINE_ROWS, k1]")
-        args = make_args(a1, a1_affine)
-        f16 = add_f16(args)
+        args, dma, f16 = prepare(a1, a1_affine)
         if FUSE_A1_AFFINE and lib.rgnn_linear_fwd_fuses_a1_affine(C.byref(args)):
             COUNTERS["fused_a1_affine"] += 1
         else:
             # (a narrow / odd-width layer on another kernel: one pass over a1 first -- same arithmetic, same kernels as before)
-            args = make_args(scale_shift_act(a1, a1_affine, relu=a1_relu), None)
-            f16 = add_f16(args)
+            args, dma, f16 = prepare(scale_shift_act(a1, a1_affine, relu=a1_relu), None)   # (other operand, other arguments: asked again)
     else:
-        args = make_args(a1, None)
-        f16 = add_f16(args)
-    if (padded_row_list or a1_affine_tiles is not None) and lib.rgnn_linear_fwd_path(C.byref(args)) == 0:
+        args, dma, f16 = prepare(a1, None)
+    if (padded_row_list or a1_affine_tiles is not None) and not dma:
         # (``row_index`` may hold -1 entries -- a segment-padded list: only the LDS-DMA kernel skips them, any other kernel would
         #  read row -1)
         raise RgnnError("a segment-padded row list needs the LDS-DMA kernel, which this launch does not qualify for")
     word = None
     # (a row-subset launch that could not track max |out| leaves rows in `out` no bound covers -- a later launch
     #  into the same `out` must not attach a fresh word that only knows its own rows)
-    if (track and lib.rgnn_linear_fwd_path(C.byref(args)) != 0       # the LDS-DMA kernel: it can track max |out|
+    if (track and dma                                                # the LDS-DMA kernel: it can track max |out|
             and not (row_index is not None and getattr(out, "_rgnn_rows_without_bound", False))):
         # (row-subset launches into a shared `out` -- the two halves of a conv layer's update -- share one word)
         word = bound_of(out) if row_index is not None else None
