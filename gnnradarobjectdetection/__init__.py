@@ -1,7 +1,7 @@
 """Import-path shim: ``gnnradarobjectdetection.graph_constructor`` and ``gnnradarobjectdetection.gnn`` resolve to the
 MI355X implementation in ``radargnn_amd`` so that code written against the reference package
 (``from gnnradarobjectdetection.gnn.gnn_models import DetNetBasic`` ...) runs unchanged.  Only the hot-path
-sub-packages exist here; the reference's pre/post-processors are out of scope.
+sub-packages exist here, with the device-side parts of the pre- and post-processor.
 
 A whole-module pickle written by the reference's trainer (gnn/trainer.py:342-354) names torch_geometric classes.  Reading one with the
 reference's own ``torch.load`` (evaluate.py:46-52) needs those paths importable; where torch_geometric is not installed,

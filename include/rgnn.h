@@ -47,6 +47,8 @@ typedef void* rgnn_stream_t; /* hipStream_t */
 #define RGNN_STATUS_GT_OBJECT_TOO_LARGE 64   /* rgnn_create_gt_boxes: an object of more than rgnn_gt_object_cap() points; its rows are not written */
 #define RGNN_STATUS_GT_DEGENERATE_OBJECT 128 /* rgnn_create_gt_boxes: two coincident points, or >= 3 points whose hull has no area (the reference
                                               * divides by zero / raises QhullError); its rows are not written */
+#define RGNN_STATUS_PREPROCESS_BAD_ROW 256   /* rgnn_accumulate_frames: a sensor_id / label_id outside its table (the row is dropped), or a
+                                              * window whose row range does not lie inside the table (the frame is empty) */
 
 #define RGNN_SPLITK_TIMEOUT_WORD 1000    /* index of the time-out counter in the flag area of rgnn_linear_args.splitk_ws */
 
@@ -972,6 +974,32 @@ int32_t rgnn_gt_object_cap(void);
 int rgnn_create_gt_boxes(const double* pos, int64_t n, const int64_t* obj_ptr, const int32_t* obj_rows, int64_t n_rows,
                          int64_t n_obj, const int32_t* nn_index /*[dev] or NULL*/, int32_t aligned, int32_t invariance,
                          double* out, double* rect /*[dev] or NULL*/, int32_t* status /*[dev]*/, rgnn_stream_t stream);
+
+/* ---------------------------------------------------------------- point-cloud frames of a sequence (csrc/preprocess.hip)
+ * create_point_cloud_frames + SceneCollection.process + PointCloudProcessor.transform (preprocessor/radarscenes/
+ * dataset_creation.py:159-184,716-783, scene_collection.py:36-156,185-230) behind the host's window plan: frame w is the rows
+ * [win_rows[2 w], win_rows[2 w + 1]) of the detection table (ranges may overlap and may be empty) that survive the filter, in row
+ * order.  Table columns as RadarScenes stores them ([dev], n_rows each); sensor_yaw: [dev] double [n_sensors] indexed by sensor_id;
+ * label_map: [dev] int32 [n_labels] indexed by label_id, the reduced class or -1 = drop.
+ * Per row, in float64: X = (x_cc, y_cc); angle = azimuth_sc + sensor_yaw[sensor_id]; V = vr_compensated * (cos angle, sin angle),
+ * one multiply per component, nothing fused.  A row is dropped if crop != 0 and (|y| > sides or x > front or x < 0) -- strict, so
+ * NaN coordinates and -0.0 stay --, if its label maps to -1, or if a component of V is NaN.
+ * Outputs ([dev], caller-owned): frame_ptr int64 [n_win + 1]; per survivor, windows in order and rows in order inside a window:
+ * X, V double [., 2], rcs_out, timestamp_out double, label_out (the mapped class), track_out, src_row (the row of the table) int32.
+ * They hold n_cap rows: size them for the sum of the windows' rows (the host knows it) and narrow them to frame_ptr[n_win] after
+ * reading it; nothing is ever written at or beyond n_cap.
+ * A sensor_id / label_id outside its table drops the row, a window outside the table is left empty; both raise
+ * RGNN_STATUS_PREPROCESS_BAD_ROW in *status, everything else is written as usual.
+ * Three launches (count, scan, write), no host read, no waiting between work-groups; the result does not depend on scheduling.
+ * tmp: [dev] rgnn_accumulate_frames_tmp_bytes(n_win) bytes. */
+int64_t rgnn_accumulate_frames_tmp_bytes(int64_t n_win);
+int rgnn_accumulate_frames(const int64_t* timestamp, const uint8_t* sensor_id, const float* azimuth_sc, const float* rcs,
+                           const float* vr_compensated, const float* x_cc, const float* y_cc, const uint8_t* label_id,
+                           const int32_t* track, int64_t n_rows, const int64_t* win_rows, int64_t n_win,
+                           const double* sensor_yaw, int32_t n_sensors, const int32_t* label_map, int32_t n_labels,
+                           int32_t crop, double front, double sides, int64_t* frame_ptr, int64_t n_cap, double* X, double* V,
+                           double* rcs_out, double* timestamp_out, int32_t* label_out, int32_t* track_out, int32_t* src_row,
+                           int32_t* status, void* tmp, rgnn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@ Sub-modules
     radargnn_amd.graph_constructor   mirror of gnnradarobjectdetection.graph_constructor (Graph / GeometricGraph)
     radargnn_amd.gnn                 mirror of gnnradarobjectdetection.gnn (MPNNConv, RadarPointGNNConv, DetNetBasic)
     radargnn_amd.frames              batched on-device pipeline: frames in HBM -> graphs -> logits / boxes
+    radargnn_amd.preprocessor        a RadarScenes sequence's detection table -> point-cloud frames, graphs and targets in HBM
     radargnn_amd.synthetic           deterministic synthetic radar frames (no dataset travels with the repo)
     radargnn_amd.checkpoint          reads the reference trainer's whole-module pickles without torch_geometric
 

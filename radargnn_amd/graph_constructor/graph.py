@@ -191,7 +191,7 @@ class GeometricGraph(Graph):
 
 
 # ---------------------------------------------------------------------------------------------------
-# the caller on the pre-processor side (out of scope as a subsystem, its call site is the boundary)
+# the k = 1 search and the per-frame builder for callers on the pre-processor side (frames from a sequence: radargnn_amd.preprocessor)
 # ---------------------------------------------------------------------------------------------------
 def nearest_neighbor_index(X: np.ndarray) -> np.ndarray:
     """Index of the nearest other point of every row of ``X`` -- the k = 1 use of the neighbour search outside the

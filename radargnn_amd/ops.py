@@ -186,6 +186,7 @@ STATUS_NOT_SYMMETRIC = 16
 STATUS_SPLITK_TIMEOUT = 32
 STATUS_GT_OBJECT_TOO_LARGE = 64
 STATUS_GT_DEGENERATE_OBJECT = 128
+STATUS_PREPROCESS_BAD_ROW = 256
 SPLITK_TIMEOUT_WORD = 1000          # rgnn.h RGNN_SPLITK_TIMEOUT_WORD
 
 
@@ -1992,6 +1993,46 @@ def create_gt_boxes(pos: torch.Tensor, obj_ptr: torch.Tensor, obj_rows: torch.Te
     check(lib.rgnn_create_gt_boxes(_ptr(pos), n, _ptr(obj_ptr), _ptr(obj_rows), obj_rows.numel(), n_obj, _ptr(nn_index),
                                    1 if aligned else 0, int(invariance), _ptr(out), _ptr(rect), _ptr(status), _stream()))
     return out, rect, status
+
+
+def accumulate_frames(columns: dict, win_rows: torch.Tensor, sensor_yaw: torch.Tensor, label_map: torch.Tensor, crop: bool,
+                      front: float, sides: float, n_cap: int, status: Optional[torch.Tensor] = None):
+    """Frames from windows of a detection table (rgnn_accumulate_frames: count, scan, write; no host read).
+    ``columns``: the table in HBM -- timestamp int64, sensor_id / label_id uint8, azimuth_sc / rcs / vr_compensated / x_cc / y_cc
+    float32, track int32, [n_rows] each; ``win_rows`` int64 [W, 2] row ranges; ``sensor_yaw`` f64 [n_sensors]; ``label_map`` int32
+    [n_labels], -1 = drop; ``n_cap``: rows to allocate, the sum of the windows' rows.
+    -> (frame_ptr int64 [W + 1], X f64 [n_cap, 2], V f64 [n_cap, 2], rcs f64, timestamp f64, label int32, track int32, src_row int32,
+    status int32 [1]); the rows beyond frame_ptr[W] are unwritten: the caller narrows after reading it, with ``status``."""
+    kinds = (("timestamp", torch.int64), ("sensor_id", torch.uint8), ("azimuth_sc", torch.float32), ("rcs", torch.float32),
+             ("vr_compensated", torch.float32), ("x_cc", torch.float32), ("y_cc", torch.float32), ("label_id", torch.uint8),
+             ("track", torch.int32))
+    cols = [_dev(columns[name], name, dtype) for name, dtype in kinds]
+    n_rows = cols[0].numel()
+    if any(c.dim() != 1 or c.numel() != n_rows or not c.is_contiguous() for c in cols):
+        raise ValueError("every table column must be contiguous [n_rows]")
+    _dev(win_rows, "win_rows", torch.int64)
+    _dev(sensor_yaw, "sensor_yaw", torch.float64)
+    _dev(label_map, "label_map", torch.int32)
+    if win_rows.dim() != 2 or win_rows.shape[1] != 2 or sensor_yaw.dim() != 1 or label_map.dim() != 1:
+        raise ValueError("win_rows must be [W, 2], sensor_yaw and label_map 1-D")
+    win_rows, sensor_yaw, label_map = win_rows.contiguous(), sensor_yaw.contiguous(), label_map.contiguous()
+    dev, n_win, n_cap = cols[0].device, win_rows.shape[0], int(n_cap)
+    frame_ptr = torch.empty(n_win + 1, dtype=torch.int64, device=dev)
+    X = torch.empty((n_cap, 2), dtype=torch.float64, device=dev)
+    V = torch.empty((n_cap, 2), dtype=torch.float64, device=dev)
+    rcs = torch.empty(n_cap, dtype=torch.float64, device=dev)
+    ts = torch.empty(n_cap, dtype=torch.float64, device=dev)
+    label = torch.empty(n_cap, dtype=torch.int32, device=dev)
+    track = torch.empty(n_cap, dtype=torch.int32, device=dev)
+    src_row = torch.empty(n_cap, dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    tmp = torch.empty(int(lib.rgnn_accumulate_frames_tmp_bytes(n_win)), dtype=torch.uint8, device=dev)
+    check(lib.rgnn_accumulate_frames(*[_ptr(c) for c in cols], n_rows, _ptr(win_rows), n_win, _ptr(sensor_yaw), sensor_yaw.numel(),
+                                     _ptr(label_map), label_map.numel(), 1 if crop else 0, float(front), float(sides),
+                                     _ptr(frame_ptr), n_cap, _ptr(X), _ptr(V), _ptr(rcs), _ptr(ts), _ptr(label), _ptr(track),
+                                     _ptr(src_row), _ptr(status), _ptr(tmp), _stream()))
+    return frame_ptr, X, V, rcs, ts, label, track, src_row, status
 
 
 def remove_duplicate_boxes(corners: torch.Tensor, box_ptr: torch.Tensor) -> torch.Tensor:
