@@ -49,6 +49,11 @@ typedef void* rgnn_stream_t; /* hipStream_t */
                                               * divides by zero / raises QhullError); its rows are not written */
 #define RGNN_STATUS_PREPROCESS_BAD_ROW 256   /* rgnn_accumulate_frames: a sensor_id / label_id outside its table (the row is dropped), or a
                                               * window whose row range does not lie inside the table (the frame is empty) */
+#define RGNN_STATUS_NUSC_BAD_CHUNK 512       /* rgnn_nusc_points: chunk_sample not non-decreasing inside [0, n_samples), or chunk_ptr not
+                                              * rising inside [0, n_total] (such a chunk is left out); rgnn_nusc_label_points: a frame_ptr
+                                              * range outside the points (the sample is left unwritten) */
+#define RGNN_STATUS_NUSC_BAD_BOX_PTR 1024    /* rgnn_nusc_boxes / rgnn_nusc_label_points: a sample's box offsets do not lie inside the box
+                                              * list (the sample is treated as one without boxes) */
 
 #define RGNN_SPLITK_TIMEOUT_WORD 1000    /* index of the time-out counter in the flag area of rgnn_linear_args.splitk_ws */
 
@@ -1000,6 +1005,49 @@ int rgnn_accumulate_frames(const int64_t* timestamp, const uint8_t* sensor_id, c
                            int32_t crop, double front, double sides, int64_t* frame_ptr, int64_t n_cap, double* X, double* V,
                            double* rcs_out, double* timestamp_out, int32_t* label_out, int32_t* track_out, int32_t* src_row,
                            int32_t* status, void* tmp, rgnn_stream_t stream);
+
+/* ---------------------------------------------------------------- nuScenes samples into labelled point clouds (csrc/nuscenes.hip)
+ * preprocessor/nuscenes/dataset_creation.py:121-165,189-201,241-278, utils.py:6-48, conversion.py:112-187.  float64 throughout.
+ *
+ * rgnn_nusc_points: points is channel-major [19, n_total] (the devkit's 18 radar channels, the timestamp beneath), laid out in
+ * chunks -- one per (sample, sensor), rows [chunk_ptr[c], chunk_ptr[c + 1]) -- with chunk_sample int32 [n_chunks] non-decreasing,
+ * chunk_rotation [n_chunks, 4] (quaternion w, x, y, z; normalised here) and chunk_translation [n_chunks, 3].  Per row: channels
+ * 0-2 are rotated and translated, channels 8-9 rotated by the upper-left 2 x 2; with crop != 0 a row is dropped if x > xlim,
+ * x < -xlim, y > ylim or y < -ylim (a row on a limit stays, NaN stays).  Outputs per survivor, samples in order and rows in order
+ * inside a sample: X (x, y), V (channels 8-9), V_cc (channels 6-7) double [., 2], rcs (channel 5), timestamp (channel 18) double,
+ * src_row int32; frame_ptr int64 [n_samples + 1].  They hold n_cap rows (size for n_total); nothing is written at or beyond n_cap.
+ * Lists that fail the check raise RGNN_STATUS_NUSC_BAD_CHUNK; a chunk outside the points is left out.
+ * Three launches (count, scan, write); tmp: [dev] rgnn_nusc_points_tmp_bytes(n_samples) bytes.
+ *
+ * rgnn_nusc_boxes: boxes in the global frame (box_center, box_size = w, l, h [n_boxes, 3], box_rotation [n_boxes, 4], box_label,
+ * box_points int32), sample s owning [box_ptr[s], box_ptr[s + 1]); ego pose per sample.  A box with box_points <= 0 is dropped; the
+ * others move to the vehicle frame (c_v = R_e^T (c - t_e), R_v = R_e^T R_box); with crop != 0 a box stays only if
+ * -xlim < c_v.x < xlim and -ylim < c_v.y < ylim.  Survivors keep list order and are written as records of
+ * rgnn_nusc_box_record_doubles() (20) doubles into records [n_boxes, 20] at [box_ptr[s], box_ptr[s] + box_count[s]):
+ *   0-2 p1 = corner 0 of corners(wlh_factor), 3-5 i = corner 4 - p1, 6-8 j = corner 1 - p1, 9 |i|, 10 |j|,
+ *   11-15 the rectangle of the bottom corners of corners(1): x_c, y_c, l, w, theta in degrees (0 <= theta <= 180),
+ *   16 label, 17 the box's index in the input list, 18-19 zero.
+ * One launch (one wave per sample).
+ *
+ * rgnn_nusc_label_points: per point of sample s (rows [frame_ptr[s], frame_ptr[s + 1]) of pos [n, 2]) the LAST record of the sample, in
+ * list order, with -offset <= i.v / |i| <= |i| + offset and the same for j, v = (x, y, 0) - p1.  label int32 [n] gets its label (0:
+ * none), out double [n, 5] its box in encoding 0 none [x_c, y_c, l, w, theta], 1 translation [x_c - x, y_c - y, l, w, theta] or 2 en
+ * [d, angle(nn -> centre), l, w, angle(nn -> long side)] (nn_index int32 [n], else NULL), NaN without a hit; hit (optional) int32 [n]
+ * the winning box's index in the input list or -1.  One launch (one work-group per sample, records staged through LDS). */
+int32_t rgnn_nusc_box_record_doubles(void);
+int64_t rgnn_nusc_points_tmp_bytes(int64_t n_samples);
+int rgnn_nusc_points(const double* points, int64_t n_total, const int64_t* chunk_ptr, const int32_t* chunk_sample,
+                     const double* chunk_rotation, const double* chunk_translation, int64_t n_chunks, int64_t n_samples,
+                     int32_t crop, double xlim, double ylim, int64_t* frame_ptr, int64_t n_cap, double* X, double* V, double* V_cc,
+                     double* rcs, double* timestamp, int32_t* src_row, int32_t* status, void* tmp, rgnn_stream_t stream);
+int rgnn_nusc_boxes(const double* box_center, const double* box_size, const double* box_rotation, const int32_t* box_label,
+                    const int32_t* box_points, const int64_t* box_ptr, int64_t n_boxes, int64_t n_samples,
+                    const double* ego_translation, const double* ego_rotation, int32_t crop, double xlim, double ylim,
+                    double wlh_factor, double* records, int32_t* box_count, int32_t* status, rgnn_stream_t stream);
+int rgnn_nusc_label_points(const double* pos, int64_t n, const int64_t* frame_ptr, int64_t n_samples, const double* records,
+                           const int64_t* box_ptr, const int32_t* box_count, int64_t n_boxes, const int32_t* nn_index /*[dev] or NULL*/,
+                           int32_t invariance, double wlh_offset, int32_t* label, double* out, int32_t* hit /*[dev] or NULL*/,
+                           int32_t* status /*[dev]*/, rgnn_stream_t stream);
 
 #ifdef __cplusplus
 }

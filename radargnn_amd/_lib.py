@@ -199,6 +199,14 @@ SIGNATURES = {
     "rgnn_accumulate_frames_tmp_bytes": (c_i64, [c_i64]),
     "rgnn_accumulate_frames": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_i32,
                                        c_i32, c_f64, c_f64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_nusc_box_record_doubles": (c_i32, []),
+    "rgnn_nusc_points_tmp_bytes": (c_i64, [c_i64]),
+    "rgnn_nusc_points": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_f64, c_f64, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_nusc_boxes": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_f64, c_f64, c_f64, c_vp, c_vp,
+                                c_vp, c_vp]),
+    "rgnn_nusc_label_points": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_f64, c_vp, c_vp, c_vp, c_vp,
+                                       c_vp]),
 }
 
 

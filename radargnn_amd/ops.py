@@ -187,6 +187,8 @@ STATUS_SPLITK_TIMEOUT = 32
 STATUS_GT_OBJECT_TOO_LARGE = 64
 STATUS_GT_DEGENERATE_OBJECT = 128
 STATUS_PREPROCESS_BAD_ROW = 256
+STATUS_NUSC_BAD_CHUNK = 512
+STATUS_NUSC_BAD_BOX_PTR = 1024
 SPLITK_TIMEOUT_WORD = 1000          # rgnn.h RGNN_SPLITK_TIMEOUT_WORD
 
 
@@ -2033,6 +2035,113 @@ def accumulate_frames(columns: dict, win_rows: torch.Tensor, sensor_yaw: torch.T
                                      _ptr(frame_ptr), n_cap, _ptr(X), _ptr(V), _ptr(rcs), _ptr(ts), _ptr(label), _ptr(track),
                                      _ptr(src_row), _ptr(status), _ptr(tmp), _stream()))
     return frame_ptr, X, V, rcs, ts, label, track, src_row, status
+
+
+def nusc_points(points: torch.Tensor, chunk_ptr: torch.Tensor, chunk_sample: torch.Tensor, chunk_rotation: torch.Tensor,
+                chunk_translation: torch.Tensor, n_samples: int, crop: bool, xlim: float, ylim: float,
+                status: Optional[torch.Tensor] = None):
+    """nuScenes radar rows into vehicle-frame, cropped point clouds (rgnn_nusc_points: count, scan, write; no host read).
+    ``points`` f64 [19, N_total] channel-major; chunks: ``chunk_ptr`` int64 [C + 1], ``chunk_sample`` int32 [C] non-decreasing,
+    ``chunk_rotation`` f64 [C, 4] (w, x, y, z), ``chunk_translation`` f64 [C, 3].
+    -> (frame_ptr int64 [B + 1], X, V, V_cc f64 [N_total, 2], rcs, timestamp f64, src_row int32, status int32 [1]); the rows beyond
+    frame_ptr[B] are unwritten: the caller narrows after reading it, with ``status`` (STATUS_NUSC_BAD_CHUNK)."""
+    _dev(points, "points", torch.float64)
+    _dev(chunk_ptr, "chunk_ptr", torch.int64)
+    _dev(chunk_sample, "chunk_sample", torch.int32)
+    _dev(chunk_rotation, "chunk_rotation", torch.float64)
+    _dev(chunk_translation, "chunk_translation", torch.float64)
+    if points.dim() != 2 or points.shape[0] != 19 or not points.is_contiguous():
+        raise ValueError("points must be contiguous [19, N_total]")
+    n_chunks = chunk_sample.numel()
+    if chunk_ptr.shape != (n_chunks + 1,) or chunk_sample.dim() != 1 or chunk_rotation.shape != (n_chunks, 4) or \
+            chunk_translation.shape != (n_chunks, 3):
+        raise ValueError("chunk_ptr [C + 1], chunk_sample [C], chunk_rotation [C, 4], chunk_translation [C, 3]")
+    chunk_ptr, chunk_sample = chunk_ptr.contiguous(), chunk_sample.contiguous()
+    chunk_rotation, chunk_translation = chunk_rotation.contiguous(), chunk_translation.contiguous()
+    dev, n_total, n_samples = points.device, points.shape[1], int(n_samples)
+    frame_ptr = torch.empty(n_samples + 1, dtype=torch.int64, device=dev)
+    X, V, V_cc = (torch.empty((n_total, 2), dtype=torch.float64, device=dev) for _ in range(3))
+    rcs, ts = (torch.empty(n_total, dtype=torch.float64, device=dev) for _ in range(2))
+    src_row = torch.empty(n_total, dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    tmp = torch.empty(int(lib.rgnn_nusc_points_tmp_bytes(n_samples)), dtype=torch.uint8, device=dev)
+    check(lib.rgnn_nusc_points(_ptr(points), n_total, _ptr(chunk_ptr), _ptr(chunk_sample), _ptr(chunk_rotation), _ptr(chunk_translation),
+                               n_chunks, n_samples, 1 if crop else 0, float(xlim), float(ylim), _ptr(frame_ptr), n_total, _ptr(X),
+                               _ptr(V), _ptr(V_cc), _ptr(rcs), _ptr(ts), _ptr(src_row), _ptr(status), _ptr(tmp), _stream()))
+    return frame_ptr, X, V, V_cc, rcs, ts, src_row, status
+
+
+def nusc_box_record_doubles() -> int:
+    """Doubles per prepared box of ``nusc_boxes`` (rgnn_nusc_box_record_doubles; the layout is in rgnn.h)."""
+    return int(lib.rgnn_nusc_box_record_doubles())
+
+
+def nusc_boxes(box_center: torch.Tensor, box_size: torch.Tensor, box_rotation: torch.Tensor, box_label: torch.Tensor,
+               box_points: torch.Tensor, box_ptr: torch.Tensor, ego_translation: torch.Tensor, ego_rotation: torch.Tensor, crop: bool,
+               xlim: float, ylim: float, wlh_factor: float, status: Optional[torch.Tensor] = None):
+    """Annotation boxes filtered, moved to the vehicle frame, cropped and prepared (rgnn_nusc_boxes, one launch).
+    -> (records f64 [M, 20], box_count int32 [B], status int32 [1]): sample s's survivors, in list order, are the records
+    [box_ptr[s], box_ptr[s] + box_count[s]); the rest of its segment is unwritten (STATUS_NUSC_BAD_BOX_PTR: no boxes)."""
+    _dev(box_center, "box_center", torch.float64)
+    _dev(box_size, "box_size", torch.float64)
+    _dev(box_rotation, "box_rotation", torch.float64)
+    _dev(box_label, "box_label", torch.int32)
+    _dev(box_points, "box_points", torch.int32)
+    _dev(box_ptr, "box_ptr", torch.int64)
+    _dev(ego_translation, "ego_translation", torch.float64)
+    _dev(ego_rotation, "ego_rotation", torch.float64)
+    m, b = box_label.numel(), box_ptr.numel() - 1
+    if box_center.shape != (m, 3) or box_size.shape != (m, 3) or box_rotation.shape != (m, 4) or box_label.dim() != 1 or \
+            box_points.shape != (m,) or box_ptr.dim() != 1 or b < 0 or ego_translation.shape != (b, 3) or ego_rotation.shape != (b, 4):
+        raise ValueError("box_center / box_size [M, 3], box_rotation [M, 4], box_label / box_points [M], box_ptr [B + 1], "
+                         "ego_translation [B, 3], ego_rotation [B, 4]")
+    t = [x.contiguous() for x in (box_center, box_size, box_rotation, box_label, box_points, box_ptr, ego_translation, ego_rotation)]
+    dev = box_ptr.device
+    records = torch.empty((m, nusc_box_record_doubles()), dtype=torch.float64, device=dev)
+    box_count = torch.zeros(b, dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib.rgnn_nusc_boxes(_ptr(t[0]), _ptr(t[1]), _ptr(t[2]), _ptr(t[3]), _ptr(t[4]), _ptr(t[5]), m, b, _ptr(t[6]), _ptr(t[7]),
+                              1 if crop else 0, float(xlim), float(ylim), float(wlh_factor), _ptr(records), _ptr(box_count),
+                              _ptr(status), _stream()))
+    return records, box_count, status
+
+
+def nusc_label_points(pos: torch.Tensor, frame_ptr: torch.Tensor, records: torch.Tensor, box_ptr: torch.Tensor,
+                      box_count: torch.Tensor, nn_index: Optional[torch.Tensor], invariance: int, wlh_offset: float,
+                      status: Optional[torch.Tensor] = None):
+    """Labels and box targets of every point in one pass (rgnn_nusc_label_points, one launch): the LAST box of the sample, in list
+    order, that contains the point.  ``pos`` f64 [N, 2]; ``frame_ptr`` int64 [B + 1]; ``records`` / ``box_count``: ``nusc_boxes``;
+    ``nn_index`` int32 [N] for the en encoding (invariance 2).
+    -> (label int32 [N] (0: no box), boxes f64 [N, 5] (NaN: no box), hit int32 [N] (the box's index in the input list, -1), status)."""
+    _dev(pos, "pos", torch.float64)
+    _dev(frame_ptr, "frame_ptr", torch.int64)
+    _dev(records, "records", torch.float64)
+    _dev(box_ptr, "box_ptr", torch.int64)
+    _dev(box_count, "box_count", torch.int32)
+    b, n, m = frame_ptr.numel() - 1, pos.shape[0], records.shape[0]
+    if pos.dim() != 2 or pos.shape[1] != 2 or not pos.is_contiguous():
+        raise ValueError("pos must be contiguous [N, 2]")
+    if records.dim() != 2 or records.shape[1] != nusc_box_record_doubles() or not records.is_contiguous():
+        raise ValueError("records must be contiguous [M, 20] (nusc_boxes)")
+    if b < 0 or frame_ptr.dim() != 1 or box_ptr.shape != (b + 1,) or box_count.shape != (b,):
+        raise ValueError("frame_ptr and box_ptr must be [B + 1], box_count [B]")
+    if nn_index is not None:
+        _dev(nn_index, "nn_index", torch.int32)
+        if nn_index.shape != (n,):
+            raise ValueError("nn_index must be [N]")
+        nn_index = nn_index.contiguous()
+    frame_ptr, box_ptr, box_count = frame_ptr.contiguous(), box_ptr.contiguous(), box_count.contiguous()
+    dev = pos.device
+    label = torch.zeros(n, dtype=torch.int32, device=dev)
+    out = torch.full((n, 5), float("nan"), dtype=torch.float64, device=dev)
+    hit = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib.rgnn_nusc_label_points(_ptr(pos), n, _ptr(frame_ptr), b, _ptr(records), _ptr(box_ptr), _ptr(box_count), m, _ptr(nn_index),
+                                     int(invariance), float(wlh_offset), _ptr(label), _ptr(out), _ptr(hit), _ptr(status), _stream()))
+    return label, out, hit, status
 
 
 def remove_duplicate_boxes(corners: torch.Tensor, box_ptr: torch.Tensor) -> torch.Tensor:
