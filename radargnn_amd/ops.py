@@ -1655,7 +1655,7 @@ def mpnn_aggregate_bwd(dM, Q, We, ea_sorted, rowptr_t, src_sorted, aggr: str, so
                 torch.zeros((d, de), dtype=torch.float32, device=dev) if de else None)
     dQ = torch.empty((n, d), dtype=torch.float32, device=dev)
     if (AGGR_CODES[aggr] == 0 and edge_maps is not None and n_edges > 0 and USE_MAX_BWD and lib.rgnn_mpnn_max_bwd_supported(d, de)
-            and dM.stride(0) % 4 == 0 and Q.stride(0) % 4 == 0):
+            and dM.stride(0) % 4 == 0 and Q.stride(0) % 4 == 0 and (dM.data_ptr() | Q.data_ptr()) % 16 == 0):
         tgt_sorted, eloc_sorted, tloc = edge_maps
         for t_, nm in ((tgt_sorted, "tgt_sorted"), (eloc_sorted, "eloc_sorted"), (tloc, "tloc")):
             _dev(t_, nm, torch.int32)
