@@ -1,1 +1,1 @@
-from radargnn_amd.gnn.configs import GNNArchitectureConfig  # noqa: F401
+from radargnn_amd.gnn.configs import GNNArchitectureConfig, TrainingConfig  # noqa: F401

@@ -1049,6 +1049,27 @@ int rgnn_nusc_label_points(const double* pos, int64_t n, const int64_t* frame_pt
                            int32_t invariance, double wlh_offset, int32_t* label, double* out, int32_t* hit /*[dev] or NULL*/,
                            int32_t* status /*[dev]*/, rgnn_stream_t stream);
 
+/* ---------------------------------------------------------------- optimizer step and target re-encoding (csrc/optim.hip)
+ * rgnn_adam_step: torch.optim.Adam with amsgrad and maximize off and the weight decay added to the gradient, for n_tensors float32
+ * tensors at once.  The tables are HOST arrays of length n_tensors, read before the call returns: device pointers of the parameter,
+ * its gradient and its two moment tensors (contiguous, numel[i] floats each, 4-byte aligned, any offset inside an allocation), the
+ * step count t of each tensor INCLUDING this step (>= 1), its learning rate and weight decay.  Per element, evaluated in double from
+ * the float32 operands with every stored value rounded once:
+ *   g = grad + wd p;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;
+ *   p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * The tables travel as kernel arguments: ceil(n / capacity) launches for the n tensors that are not empty, capacity =
+ * rgnn_adam_capacity (64); *launches (host, optional) receives the number made.  No allocation, no copy, no synchronisation.
+ *
+ * rgnn_adapt_orientation_angle: adapt_bb_orientation_angle (preprocessor/bounding_box.py:536-563) on y = [n, width] float32 rows
+ * (label | box, width >= 6), out of place: every row is copied bit for bit, and where y[i, 1] is not NaN, out[i, 5] =
+ * sin(y[i, 5] > pi / 2 ? y[i, 5] - pi : y[i, 5]), compared, subtracted and evaluated in double, rounded once.  One launch. */
+int32_t rgnn_adam_capacity(void);
+int rgnn_adam_step(int64_t n_tensors, void* const* param, const void* const* grad, void* const* exp_avg, void* const* exp_avg_sq,
+                   const int64_t* numel, const int64_t* step, const double* lr, const double* weight_decay, double beta1,
+                   double beta2, double eps, int32_t* launches /*[host] or NULL*/, rgnn_stream_t stream);
+int rgnn_adapt_orientation_angle(const float* y, int64_t ldy, float* out, int64_t ldo, int64_t n, int32_t width,
+                                 rgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2346,3 +2346,57 @@ def detection_loss_bwd(cls, boxes, y, class_weight, bg_index, delta, cls_loss_we
                                       float(cls_loss_weight), float(bb_loss_weight), _ptr(sums), _ptr(g), _ptr(d_cls), k,
                                       _ptr(d_bb), w, _stream()))
     return d_cls, d_bb
+
+
+# ---- optimizer step and target re-encoding (csrc/optim.hip) ----------------------------------------------------------------------
+def adam_capacity() -> int:
+    """Tensors one launch of ``adam_step`` covers."""
+    return int(lib.rgnn_adam_capacity())
+
+
+def adam_step(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], exp_avgs: Sequence[torch.Tensor],
+              exp_avg_sqs: Sequence[torch.Tensor], steps: Sequence[int], lrs: Sequence[float], weight_decays: Sequence[float],
+              beta1: float, beta2: float, eps: float) -> int:
+    """One Adam step (L2 decay added to the gradient) on every listed tensor, in place; -> the number of launches made
+    (rgnn_adam_step: ceil(T / adam_capacity())).  ``steps`` are the tensors' step counts including this one.  The addresses are
+    read now, so gradients may be new tensors every step; nothing waits for the device.  The caller bumps the parameters' version
+    counters (``radargnn_amd.optim.FusedAdam`` does)."""
+    t = len(params)
+    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(steps) == len(lrs) == len(weight_decays) == t):
+        raise ValueError("one gradient, two moments, a step count, a learning rate and a weight decay per parameter")
+    if t == 0:
+        return 0
+    for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs):
+        for x, name in ((p, "parameter"), (g, "gradient"), (m, "exp_avg"), (v, "exp_avg_sq")):
+            if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.layout != torch.strided \
+                    or not x.is_contiguous() or x.device != p.device or x.shape != p.shape:
+                raise TypeError(f"adam_step: every {name} must be a contiguous float32 tensor on the parameter's GPU with the "
+                                f"parameter's shape (got {_describe(x)})")
+    table = lambda ts: (C.c_void_p * t)(*[x.data_ptr() for x in ts])
+    launches = C.c_int32(0)
+    check(lib.rgnn_adam_step(t, table(params), table(grads), table(exp_avgs), table(exp_avg_sqs),
+                             (C.c_int64 * t)(*[p.numel() for p in params]), (C.c_int64 * t)(*steps), (C.c_double * t)(*lrs),
+                             (C.c_double * t)(*weight_decays), float(beta1), float(beta2), float(eps), C.byref(launches),
+                             _stream()))
+    return launches.value
+
+
+def _describe(x) -> str:
+    if not isinstance(x, torch.Tensor):
+        return type(x).__name__
+    return f"{x.dtype} {tuple(x.shape)} on {x.device}, {'contiguous' if x.layout == torch.strided and x.is_contiguous() else 'not contiguous'}"
+
+
+def adapt_orientation_angle(y: torch.Tensor) -> torch.Tensor:
+    """``adapt_bb_orientation_angle`` (preprocessor/bounding_box.py:536-563) on a batch's ``y`` = [N, 1 + 5] (label | rotated box):
+    a NEW tensor whose angle column holds sin(theta > pi / 2 ? theta - pi : theta) in the rows that carry a box (first box column
+    not NaN), evaluated in double; everything else is copied bit for bit (rgnn_adapt_orientation_angle, one launch)."""
+    y = _dev(y, "y", torch.float32)
+    if y.dim() != 2 or y.shape[1] < 6:
+        raise ValueError(f"y must be [N, 1 + box] with a rotated box of at least 5 columns (got {tuple(y.shape)}): aligned boxes "
+                         "carry no orientation angle")
+    y = _rowmajor(y, "y")
+    out = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+    n, w = y.shape
+    check(lib.rgnn_adapt_orientation_angle(_ptr(y), _ld(y) if n > 1 else w, _ptr(out), w, n, w, _stream()))
+    return out

@@ -1,5 +1,10 @@
 """Time one training step (trainer.py:175-231 shape: forward, cross-entropy + Huber, backward, Adam) of the C2 workload
-on the HIP path.  Not the headline metric (that is bench.py, inference); a measurement for MEASUREMENTS.md section 8."""
+on the HIP path.  Not the headline metric (that is bench.py, inference); a measurement for MEASUREMENTS.md section 8.
+
+    python tools/train_step_bench.py [steps] [adam|fused|ab]
+
+adam (default): torch.optim.Adam; fused: radargnn_amd.optim.FusedAdam (one launch per step); ab: both on the same model and batch,
+in alternating rounds of `steps` steps after a warm-up of each, one line per round -- the rounds show the run-to-run spread."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -17,7 +22,19 @@ label = torch.randint(0, 6, (n,), device="cuda")
 box = torch.randn(n, 5, device="cuda")
 y = torch.cat((label.float().view(-1, 1), box), 1)              # graph_batch.y: label | box (trainer.py:185-186)
 from radargnn_amd.gnn.losses import detection_loss
-opt = torch.optim.Adam(model.parameters(), lr=1e-3)
+which = sys.argv[2] if len(sys.argv) > 2 else "adam"
+if which not in ("adam", "fused", "ab"):
+    sys.exit(f"unknown optimizer {which!r}: adam, fused or ab")
+
+
+def make_optimizer(name):
+    if name == "fused":
+        from radargnn_amd.optim import FusedAdam
+        return FusedAdam(model.parameters(), lr=1e-3)
+    return torch.optim.Adam(model.parameters(), lr=1e-3)
+
+
+opt = make_optimizer("adam" if which == "ab" else which)
 x, ei, ea = g.x, g.edge_index, g.edge_attr
 
 
@@ -30,6 +47,30 @@ def step():
     opt.step()
     return loss
 
+
+def timed_round():
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3
+
+
+if which == "ab":
+    optimizers = {"adam": opt, "fused": make_optimizer("fused")}
+    for opt in optimizers.values():
+        for _ in range(3):
+            step()
+    rounds = {name: [] for name in optimizers}
+    for r in range(6):
+        for name in (("adam", "fused") if r % 2 == 0 else ("fused", "adam")):
+            opt = optimizers[name]
+            rounds[name].append(timed_round())
+    for name, ms in rounds.items():
+        print(f"{name:5s} train step ms per round: " + " ".join(f"{v:.3f}" for v in ms) +
+              f" | median {sorted(ms)[len(ms) // 2]:.3f} min {min(ms):.3f} max {max(ms):.3f}")
+    sys.exit(0)
 
 for _ in range(2):
     step()
