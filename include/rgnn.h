@@ -751,6 +751,22 @@ int64_t rgnn_nms_mask_words(int64_t m);
 int rgnn_box_representations(const double* corners, int64_t m, double* two_point, double* rotated, rgnn_stream_t stream);
 int rgnn_nms(const void* boxes, int32_t kind, const int64_t* order, int64_t m, double iou_threshold, uint64_t* mask_tmp,
              int64_t* keep, int64_t* count, rgnn_stream_t stream);
+/* Segmented suppression: for every frame of a batch what nonzero(keep) -> rgnn_box_representations -> the reference's shift
+ * of negative coordinates (postprocessing.py:358-361, 391-394; the frame's OWN minimum) -> rgnn_sort_scores -> rgnn_nms compute
+ * for that frame alone, bit for bit, in two launches whatever n_frames is.  label / score / keep / corners: the outputs of
+ * rgnn_decode_predictions for all n nodes; frame_ptr: [dev] int64 [n_frames + 1] node offsets.  kind as in rgnn_nms: 0 aligned
+ * (scores_out float32 [n], corners_out float32 [n, 4, 2] rebuilt from the float32 two-point matrix minus the float32 shift, corner
+ * order (x0,y0) (x0,y1) (x1,y0) (x1,y1)), 1 rotated (scores_out float64 [n], corners_out float64 [n, 4, 2] copied from corners).
+ * node: int64 [n] node ids kept, frame after frame, in suppression order; labels_out: float64 [n]; only the first
+ * meta[n_frames] entries of the four outputs are written.  meta: [dev] int64 [2 n_frames + 1] = offsets of the frames' kept boxes
+ * [n_frames + 1] | candidates (keep != 0) per frame [n_frames].  A frame of more than rgnn_nms_frames_max_candidates()
+ * candidates is left empty: the caller sees its count in meta and runs it through rgnn_nms.
+ * tmp: [dev] rgnn_nms_frames_tmp_bytes(n, n_frames) bytes. */
+int64_t rgnn_nms_frames_max_candidates(void);
+int64_t rgnn_nms_frames_tmp_bytes(int64_t n, int64_t n_frames);
+int rgnn_nms_frames(const int32_t* label, const float* score, const int32_t* keep, const double* corners,
+                    const int64_t* frame_ptr, int64_t n, int64_t n_frames, int32_t kind, double iou_threshold, void* tmp,
+                    int64_t* node, double* labels_out, void* scores_out, void* corners_out, int64_t* meta, rgnn_stream_t stream);
 
 /* ================================================================ evaluation: ground truth and point IoU
  * Ground-truth boxes of one graph / batch (GroundTruthExtractor.get_absolute_object_bounding_boxes,

@@ -175,6 +175,9 @@ SIGNATURES = {
     "rgnn_sort_scores": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_vp, c_vp]),
     "rgnn_nms_mask_words": (c_i64, [c_i64]),
     "rgnn_nms": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_f64, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_nms_frames_max_candidates": (c_i64, []),
+    "rgnn_nms_frames_tmp_bytes": (c_i64, [c_i64, c_i64]),
+    "rgnn_nms_frames": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rgnn_decode_ground_truth": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rgnn_remove_duplicate_boxes": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "rgnn_point_iou_tmp_bytes": (c_i64, [c_i64, c_i32, c_i64, c_i64]),

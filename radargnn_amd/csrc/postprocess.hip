@@ -317,19 +317,18 @@ namespace {
 // 540) for all boxes at once: [x_min, y_min, x_max, y_max] and [x_centre, y_centre, l, w, theta in [0, 180]] per box.
 // l / w: the two shorter of the distances corner 1 -> corners 2, 3, 4 (the longest is the diagonal); theta: direction of
 // the side of length l; a box whose l matches none of the three (NaN corners) becomes the reference's default [0,0,1,1,0].
-__global__ __launch_bounds__(256) void k_box_repr(const double* __restrict__ corners, int64_t m, double* __restrict__ two_point,
-                                                 double* __restrict__ rotated) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
+// One box: corners c[8] -> two_point tp[4] and / or rotated o[5] (either may be null).  Shared by k_box_repr and the segmented
+// suppression kernel, so both see the same bits.
+__device__ __forceinline__ void box_repr(const double* __restrict__ c, double* __restrict__ tp, double* __restrict__ o) {
   double x[4], y[4];
-  for (int q = 0; q < 4; q++) { x[q] = corners[i * 8 + 2 * q]; y[q] = corners[i * 8 + 2 * q + 1]; }
-  if (two_point) {
-    two_point[i * 4 + 0] = fmin(fmin(x[0], x[1]), fmin(x[2], x[3]));
-    two_point[i * 4 + 1] = fmin(fmin(y[0], y[1]), fmin(y[2], y[3]));
-    two_point[i * 4 + 2] = fmax(fmax(x[0], x[1]), fmax(x[2], x[3]));
-    two_point[i * 4 + 3] = fmax(fmax(y[0], y[1]), fmax(y[2], y[3]));
+  for (int q = 0; q < 4; q++) { x[q] = c[2 * q]; y[q] = c[2 * q + 1]; }
+  if (tp) {
+    tp[0] = fmin(fmin(x[0], x[1]), fmin(x[2], x[3]));
+    tp[1] = fmin(fmin(y[0], y[1]), fmin(y[2], y[3]));
+    tp[2] = fmax(fmax(x[0], x[1]), fmax(x[2], x[3]));
+    tp[3] = fmax(fmax(y[0], y[1]), fmax(y[2], y[3]));
   }
-  if (rotated) {
+  if (o) {
     double d[3];
     for (int q = 0; q < 3; q++) {
       const double dx = x[0] - x[q + 1], dy = y[0] - y[q + 1];
@@ -345,7 +344,6 @@ __global__ __launch_bounds__(256) void k_box_repr(const double* __restrict__ cor
     int side = -1;                                         // first of d1, d2, d3 equal to l
     for (int q = 2; q >= 0; q--)
       if (d[q] == l) side = q;
-    double* o = rotated + i * 5;
     if (side < 0) { o[0] = 0; o[1] = 0; o[2] = 1; o[3] = 1; o[4] = 0; return; }
     const double vx = x[0] - x[side + 1], vy = y[0] - y[side + 1];
     const double nrm = sqrt(vx * vx + vy * vy);
@@ -355,6 +353,13 @@ __global__ __launch_bounds__(256) void k_box_repr(const double* __restrict__ cor
     o[1] = (y[0] + y[1] + y[2] + y[3]) / 4;
     o[2] = l; o[3] = w; o[4] = theta;
   }
+}
+
+__global__ __launch_bounds__(256) void k_box_repr(const double* __restrict__ corners, int64_t m, double* __restrict__ two_point,
+                                                 double* __restrict__ rotated) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  box_repr(corners + i * 8, two_point ? two_point + i * 4 : nullptr, rotated ? rotated + i * 5 : nullptr);
 }
 }  // namespace
 
@@ -487,6 +492,355 @@ extern "C" int rgnn_nms(const void* boxes, int32_t kind, const int64_t* order, i
                        (unsigned long long*)mask_tmp, words);
   hipLaunchKernelGGL(k_nms_reduce, dim3(1), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)mask_tmp, order, m,
                      words, keep, count);
+  RGNN_CHECK_LAUNCH();
+  return RGNN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Segmented suppression: what Postprocessor._finish -> BoxSuppressor.apply_nms computes for one frame, for every frame of a
+// batch in two launches, whatever the number of frames.  k_nms_frames, one work-group per frame: (1) order-preserving
+// compaction of the frame's nodes with keep != 0 into the frame's own slots [frame_ptr[f], ...); (2) box_repr per candidate,
+// the frame's own minimum (NaN propagates, as torch.min) and shift; (3) bitonic sort of (score_key, candidate) in LDS, the
+// order of rgnn_sort_scores; (4) the greedy walk of k_nms_reduce, 64 sorted candidates at a time, with the IoUs computed
+// where they are needed instead of an M x M mask: the tile's diagonal (the tile's boxes staged in LDS; lane = row, the waves
+// share the columns), then every later candidate not yet removed against the boxes the tile kept (lane = candidate, the
+// waves share the kept boxes).  The earlier box is the first argument of the IoU, as in k_nms_mask; rotated pairs too far
+// apart to touch are decided without it (far_apart), the others are collected and evaluated one pair per lane.
+// k_nms_frames_emit: offsets of the kept boxes of every frame and the gathered outputs.  A frame of more than SORT_CHUNK
+// candidates is left empty (its candidate count tells the host).
+// ------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int NMSF_THREADS = 1024;
+constexpr int NMSF_WAVES = NMSF_THREADS / 64;
+
+struct NmsFramesParams {
+  const int32_t* label; const float* score; const int32_t* keep; const double* corners;
+  const int64_t* frame_ptr; int64_t n; int64_t n_frames;
+  double thr;
+  int32_t* cand_node;        // [n]    slot -> node id; the slots of frame f start at frame_ptr[f]
+  int32_t* kept_slot;        // [n]    slots kept, in suppression order, from frame_ptr[f]
+  double* rep64;             // [n, 5] float64 representation (shifted in place for rotated boxes)
+  float* rep32;              // [n, 4] aligned boxes: the shifted matrix rounded to float32
+  double* shift;             // [n_frames]
+  int32_t* kept_cnt;         // [n_frames]
+  int64_t* node_out; double* labels_out; void* scores_out; void* corners_out;
+  int64_t* meta;             // kept_ptr [n_frames + 1] | candidates per frame [n_frames]
+};
+
+// Rotated boxes whose centres lie further apart than their circumscribed circles reach, by a margin (5e-5 of that reach) far
+// above the rounding of iou_rotated's own arithmetic (1e-16 of the coordinates about the pair's common centre): the clip in
+// iou_rotated leaves nothing, so it returns 0, at most a sliver of rounding; for a threshold above NMSF_FAR_MIN_THR
+// `iou_rotated(p, q) >= thr` is then false and the evaluation is skipped (at radar densities that is nearly every pair).
+// NaN or infinite input compares false here and takes the full evaluation.
+constexpr double NMSF_FAR_MIN_THR = 1e-9;
+__device__ __forceinline__ double circumradius(const double* b) { return 0.5 * sqrt(b[2] * b[2] + b[3] * b[3]); }
+__device__ __forceinline__ bool far_apart(const double* p, double rp, const double* q, double rq) {
+  const double dx = p[0] - q[0], dy = p[1] - q[1], r = rp + rq;
+  return dx * dx + dy * dy > 1.0001 * (r * r);
+}
+
+// One body of iou_rotated for the four places of k_nms_frames that need it (inlined four times it spills 1 KB per lane).
+__device__ __noinline__ bool rotated_hit(const double* p, const double* q, double thr) { return iou_rotated(p, q) >= thr; }
+
+__device__ __forceinline__ int64_t clamp_ptr(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+template <int KIND>
+__global__ __launch_bounds__(NMSF_THREADS) void k_nms_frames(const NmsFramesParams p) {
+  using T = typename std::conditional<KIND == 0, float, double>::type;
+  constexpr int BW = KIND == 0 ? 4 : 5;
+  __shared__ unsigned long long sk[SORT_CHUNK];
+  __shared__ unsigned si[SORT_CHUNK];
+  __shared__ unsigned long long removed[SORT_CHUNK / 64];
+  __shared__ unsigned long long diag[64];
+  __shared__ T tbox[64][BW];
+  __shared__ double tbox_r[64];
+  __shared__ int kidx[64];
+  __shared__ int n_pairs;
+  __shared__ double red_min[NMSF_WAVES];
+  __shared__ int red_i[NMSF_WAVES];
+  __shared__ unsigned long long kept_bits;
+  const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t a = clamp_ptr(p.frame_ptr[f], 0, p.n), b = clamp_ptr(p.frame_ptr[f + 1], a, p.n);
+
+  // (1) candidates, in node order
+  int m = 0;
+  for (int64_t base = a; base < b; base += NMSF_THREADS) {
+    const int64_t i = base + t;
+    const bool flag = i < b && p.keep[i] != 0;
+    const unsigned long long bal = __ballot(flag);
+    if (lane == 0) red_i[wave] = __popcll(bal);
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int w = 0; w < NMSF_WAVES; w++) {
+      const int c = red_i[w];
+      if (w < wave) before += c;
+      total += c;
+    }
+    if (flag) p.cand_node[a + m + before + __popcll(bal & ((1ull << lane) - 1ull))] = (int32_t)i;
+    m += total;
+    __syncthreads();
+  }
+  if (t == 0) p.meta[p.n_frames + 1 + f] = m;
+  if (m == 0 || m > SORT_CHUNK) {
+    if (t == 0) { p.kept_cnt[f] = 0; p.shift[f] = 0.0; }
+    return;
+  }
+
+  // (2) representation, the frame's minimum and shift (postprocessing.py:358-361, 391-394)
+  double lo = INFINITY;
+  bool has_nan = false;
+  for (int c = t; c < m; c += NMSF_THREADS) {
+    const int64_t slot = a + c;
+    const double* src = p.corners + (int64_t)p.cand_node[slot] * 8;
+    double r[5];
+    if constexpr (KIND == 0) box_repr(src, r, nullptr);
+    else box_repr(src, nullptr, r);
+    constexpr int NMIN = KIND == 0 ? 4 : 2;
+    for (int q = 0; q < NMIN; q++) {
+      if (r[q] != r[q]) has_nan = true;
+      else lo = fmin(lo, r[q]);
+    }
+    for (int q = 0; q < BW; q++) p.rep64[slot * 5 + q] = r[q];
+  }
+  for (int o = 32; o > 0; o >>= 1) lo = fmin(lo, __shfl_xor(lo, o, 64));
+  const bool wave_nan = __ballot(has_nan) != 0ull;
+  if (lane == 0) { red_min[wave] = lo; red_i[wave] = wave_nan ? 1 : 0; }
+  for (int w = t; w < SORT_CHUNK / 64; w += NMSF_THREADS) removed[w] = 0ull;
+  __syncthreads();
+  bool any_nan = false;
+  for (int w = 0; w < NMSF_WAVES; w++) { lo = fmin(lo, red_min[w]); any_nan = any_nan || red_i[w] != 0; }
+  const double shift = (!any_nan && lo < 0) ? fabs(lo) + 100.0 : 0.0;
+  if (t == 0) p.shift[f] = shift;
+  for (int c = t; c < m; c += NMSF_THREADS) {           // (the rows this thread wrote above)
+    const int64_t slot = a + c;
+    if constexpr (KIND == 1) {
+      if (shift != 0.0) { p.rep64[slot * 5] += shift; p.rep64[slot * 5 + 1] += shift; }
+    } else {
+      for (int q = 0; q < 4; q++) {
+        const double v = p.rep64[slot * 5 + q];
+        p.rep32[slot * 4 + q] = (float)(shift != 0.0 ? v + shift : v);
+      }
+    }
+  }
+
+  // (3) order: the network of k_sort_chunk over the next power of two (padding sorts after every real pair)
+  int p2 = 1;
+  while (p2 < m) p2 <<= 1;
+  for (int c = t; c < p2; c += NMSF_THREADS) {
+    if (c < m) { sk[c] = score_key((double)p.score[p.cand_node[a + c]]); si[c] = (unsigned)c; }
+    else { sk[c] = 0ull; si[c] = 0xffffffffu; }
+  }
+  __syncthreads();
+  for (int k = 2; k <= p2; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int c = t; c < p2; c += NMSF_THREADS) {
+        const int q = c ^ j;
+        if (q > c) {
+          const bool up = ((c & k) == 0);
+          const unsigned long long ka = sk[c], kb = sk[q];
+          const unsigned ia = si[c], ib = si[q];
+          if (sort_before(kb, ib, ka, ia) == up) { sk[c] = kb; si[c] = ib; sk[q] = ka; si[q] = ia; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+  // (4) greedy suppression over the sorted candidates.  Rotated pairs that may touch wait in a list (the space of the sort
+  // keys, which are dead) and get their IoU one pair per lane: evaluated where they are found, a wave would run iou_rotated
+  // for one or two of its lanes.  A full list only means that the rest is evaluated in place.
+  const T* rep = KIND == 0 ? (const T*)p.rep32 : (const T*)p.rep64;
+  const float thr32 = (float)p.thr;
+  const bool skip_far = p.thr > NMSF_FAR_MIN_THR;
+  volatile unsigned long long* removed_now = removed;
+  unsigned* pairs = (unsigned*)sk;                         // (first << 16) | second
+  constexpr int PAIR_CAP = SORT_CHUNK * 2;
+  int n_keep = 0;
+  const int tiles = (m + 63) / 64;
+  for (int bt = 0; bt < tiles; bt++) {
+    const int nrow = m - bt * 64 < 64 ? m - bt * 64 : 64;
+    if (t < 64) {                                          // the tile's boxes
+      diag[t] = 0ull;
+      if (t < nrow) {
+        const T* src = rep + (a + si[bt * 64 + t]) * BW;
+        for (int q = 0; q < BW; q++) tbox[t][q] = src[q];
+        if constexpr (KIND == 1) tbox_r[t] = circumradius(tbox[t]);
+      }
+      if (t == 0) n_pairs = 0;
+    }
+    __syncthreads();
+    const unsigned long long cur0 = removed[bt];
+    if (lane < nrow && !((cur0 >> lane) & 1ull)) {       // diagonal tile: row = lane, the waves share the columns
+      unsigned long long bits = 0ull;
+      for (int c = lane + 1 + wave; c < nrow; c += NMSF_WAVES) {
+        if ((cur0 >> c) & 1ull) continue;
+        if constexpr (KIND == 0) {
+          if (iou_aligned(tbox[lane], tbox[c]) > thr32) bits |= 1ull << c;
+        } else if (!(skip_far && far_apart(tbox[lane], tbox_r[lane], tbox[c], tbox_r[c]))) {
+          const int e = atomicAdd(&n_pairs, 1);
+          if (e < PAIR_CAP) pairs[e] = ((unsigned)lane << 16) | (unsigned)c;
+          else if (rotated_hit(tbox[lane], tbox[c], p.thr)) bits |= 1ull << c;
+        }
+      }
+      if (bits) atomicOr(&diag[lane], bits);
+    }
+    if constexpr (KIND == 1) {
+      __syncthreads();
+      const int np = n_pairs < PAIR_CAP ? n_pairs : PAIR_CAP;
+      for (int e = t; e < np; e += NMSF_THREADS) {
+        const int row = (int)(pairs[e] >> 16), c = (int)(pairs[e] & 0xffffu);
+        if (rotated_hit(tbox[row], tbox[c], p.thr)) atomicOr(&diag[row], 1ull << c);
+      }
+    }
+    __syncthreads();
+    if (t < 64) {                                          // in-tile greedy pass (wave 0), as k_nms_reduce
+      const unsigned long long d = diag[lane];
+      unsigned long long cur = cur0, kb = 0ull;
+      for (int l = 0; l < nrow; l++) {
+        const unsigned long long row = __shfl(d, l, 64);
+        if (!((cur >> l) & 1ull)) { kb |= 1ull << l; cur |= row; }
+      }
+      if ((kb >> lane) & 1ull) {
+        const int rank = __popcll(kb & ((1ull << lane) - 1ull));
+        p.kept_slot[a + n_keep + rank] = (int32_t)(a + si[bt * 64 + lane]);
+        kidx[rank] = lane;
+      }
+      if (lane == 0) { kept_bits = kb; n_pairs = 0; }
+    }
+    __syncthreads();
+    const unsigned long long kb = kept_bits;
+    const int nk = __popcll(kb);
+    n_keep += nk;
+    for (int j0 = (bt + 1) * 64; j0 < m; j0 += 64) {       // later candidates: lane = candidate, the waves share the kept boxes
+      const int j = j0 + lane;
+      if (j < m && wave < nk && !((removed_now[j0 >> 6] >> lane) & 1ull)) {
+        T mine[BW];
+        const T* src = rep + (a + si[j]) * BW;
+        for (int q = 0; q < BW; q++) mine[q] = src[q];
+        bool hit = false;
+        if constexpr (KIND == 0) {
+          for (int r = wave; r < nk && !hit; r += NMSF_WAVES) hit = iou_aligned(tbox[kidx[r]], mine) > thr32;
+        } else {
+          const double my_r = circumradius(mine);
+          for (int r = wave; r < nk; r += NMSF_WAVES) {
+            const int k = kidx[r];
+            if (skip_far && far_apart(tbox[k], tbox_r[k], mine, my_r)) continue;
+            const int e = atomicAdd(&n_pairs, 1);
+            if (e < PAIR_CAP) pairs[e] = ((unsigned)j << 16) | (unsigned)k;
+            else if (!hit) hit = rotated_hit(tbox[k], mine, p.thr);
+          }
+        }
+        if (hit) atomicOr(&removed[j0 >> 6], 1ull << lane);
+      }
+    }
+    if constexpr (KIND == 1) {
+      __syncthreads();
+      const int np = n_pairs < PAIR_CAP ? n_pairs : PAIR_CAP;
+      for (int e = t; e < np; e += NMSF_THREADS) {
+        const int j = (int)(pairs[e] >> 16), k = (int)(pairs[e] & 0xffffu);
+        if ((removed_now[j >> 6] >> (j & 63)) & 1ull) continue;
+        T mine[BW];
+        const T* src = rep + (a + si[j]) * BW;
+        for (int q = 0; q < BW; q++) mine[q] = src[q];
+        if (rotated_hit(tbox[k], mine, p.thr)) atomicOr(&removed[j >> 6], 1ull << (j & 63));
+      }
+    }
+    __syncthreads();
+  }
+  if (t == 0) p.kept_cnt[f] = n_keep;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_nms_frames_emit(const NmsFramesParams p) {
+  __shared__ long long red[256];
+  const int f = blockIdx.x, t = threadIdx.x;
+  long long part = 0;
+  for (int i = t; i < f; i += 256) part += p.kept_cnt[i];
+  red[t] = part;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) red[t] += red[t + s];
+    __syncthreads();
+  }
+  const int64_t offset = red[0];
+  const int cnt = p.kept_cnt[f];
+  if (t == 0) {
+    p.meta[f] = offset;
+    if (f == p.n_frames - 1) p.meta[f + 1] = offset + cnt;
+  }
+  const int64_t a = clamp_ptr(p.frame_ptr[f], 0, p.n);
+  const double shift = p.shift[f];
+  for (int k = t; k < cnt; k += 256) {
+    const int64_t slot = p.kept_slot[a + k], node = p.cand_node[slot], o = offset + k;
+    p.node_out[o] = node;
+    p.labels_out[o] = (double)p.label[node];
+    if constexpr (KIND == 1) {                             // rotated: the decoded corners, float64 scores
+      ((double*)p.scores_out)[o] = (double)p.score[node];
+      for (int q = 0; q < 8; q++) ((double*)p.corners_out)[o * 8 + q] = p.corners[node * 8 + q];
+    } else {                                               // aligned: rebuilt from the float32 matrix (postprocessing.py:416-423)
+      ((float*)p.scores_out)[o] = p.score[node];
+      float v[4];
+      for (int q = 0; q < 4; q++) v[q] = p.rep32[slot * 4 + q];
+      if (shift != 0.0) {
+        const float s32 = (float)shift;
+        for (int q = 0; q < 4; q++) v[q] = v[q] - s32;
+      }
+      float* out = (float*)p.corners_out + o * 8;
+      out[0] = v[0]; out[1] = v[1]; out[2] = v[0]; out[3] = v[3];
+      out[4] = v[2]; out[5] = v[1]; out[6] = v[2]; out[7] = v[3];
+    }
+  }
+}
+
+struct NmsFramesTmp { int64_t cand_node, kept_slot, rep64, rep32, shift, kept_cnt, total; };
+NmsFramesTmp nms_frames_tmp(int64_t n, int64_t n_frames) {
+  NmsFramesTmp l;
+  int64_t at = 0;
+  auto take = [&](int64_t bytes) { const int64_t here = at; at = rgnn_align_up(at + bytes, 256); return here; };
+  l.cand_node = take(n * 4);
+  l.kept_slot = take(n * 4);
+  l.rep64 = take(n * 40);
+  l.rep32 = take(n * 16);
+  l.shift = take(n_frames * 8);
+  l.kept_cnt = take(n_frames * 4);
+  l.total = at + 256;
+  return l;
+}
+}  // namespace
+
+extern "C" int64_t rgnn_nms_frames_max_candidates(void) { return SORT_CHUNK; }
+
+extern "C" int64_t rgnn_nms_frames_tmp_bytes(int64_t n, int64_t n_frames) {
+  return nms_frames_tmp(n < 0 ? 0 : n, n_frames < 0 ? 0 : n_frames).total;
+}
+
+extern "C" int rgnn_nms_frames(const int32_t* label, const float* score, const int32_t* keep, const double* corners,
+                               const int64_t* frame_ptr, int64_t n, int64_t n_frames, int32_t kind, double iou_threshold,
+                               void* tmp, int64_t* node, double* labels_out, void* scores_out, void* corners_out, int64_t* meta,
+                               rgnn_stream_t stream) {
+  RGNN_CHECK_ARG(kind == 0 || kind == 1, "kind: 0 aligned (float32 corners and scores out), 1 rotated (float64 out)");
+  RGNN_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 31) && n_frames >= 0 && n_frames < ((int64_t)1 << 31), "bad sizes");
+  RGNN_CHECK_ARG(meta != nullptr, "null pointers");
+  if (n_frames == 0) {
+    hipMemsetAsync(meta, 0, 8, (hipStream_t)stream);
+    return RGNN_OK;
+  }
+  RGNN_CHECK_ARG(frame_ptr && tmp, "null pointers");
+  RGNN_CHECK_ARG(n == 0 || (label && score && keep && corners && node && labels_out && scores_out && corners_out), "null pointers");
+  const NmsFramesTmp l = nms_frames_tmp(n, n_frames);
+  char* base = (char*)tmp;
+  NmsFramesParams p{label, score, keep, corners, frame_ptr, n, n_frames, iou_threshold,
+                    (int32_t*)(base + l.cand_node), (int32_t*)(base + l.kept_slot), (double*)(base + l.rep64),
+                    (float*)(base + l.rep32), (double*)(base + l.shift), (int32_t*)(base + l.kept_cnt),
+                    node, labels_out, scores_out, corners_out, meta};
+  hipStream_t s = (hipStream_t)stream;
+  if (kind == 0) {
+    hipLaunchKernelGGL(k_nms_frames<0>, dim3((unsigned)n_frames), dim3(NMSF_THREADS), 0, s, p);
+    hipLaunchKernelGGL(k_nms_frames_emit<0>, dim3((unsigned)n_frames), dim3(256), 0, s, p);
+  } else {
+    hipLaunchKernelGGL(k_nms_frames<1>, dim3((unsigned)n_frames), dim3(NMSF_THREADS), 0, s, p);
+    hipLaunchKernelGGL(k_nms_frames_emit<1>, dim3((unsigned)n_frames), dim3(256), 0, s, p);
+  }
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
 }

@@ -1912,6 +1912,44 @@ def nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float, rotated
     return keep[:int(count.item())]
 
 
+def nms_frames_max_candidates() -> int:
+    """Candidates of one frame ``nms_frames`` suppresses itself (rgnn_nms_frames_max_candidates)."""
+    return int(lib.rgnn_nms_frames_max_candidates())
+
+
+def nms_frames(label: torch.Tensor, score: torch.Tensor, keep: torch.Tensor, corners: torch.Tensor, frame_ptr: torch.Tensor,
+               iou_threshold: float, rotated: bool):
+    """Greedy NMS of every frame of a batch in two launches (rgnn_nms_frames) on the outputs of ``decode_predictions``:
+    label int32 [N], score f32 [N], keep int32 [N], corners f64 [N, 4, 2]; ``frame_ptr`` int64 [B + 1] on the device.
+    -> (node int64 [K] ids kept, frame after frame in suppression order; labels f64 [K]; scores f64 [K] (rotated) or f32 [K]
+    (aligned); corners [K, 4, 2], the decoded float64 corners (rotated) or the float32 rebuild (aligned); ptr int64 [B + 1]
+    offsets of the frames in K, on the HOST; candidates int64 [B] per frame, on the host).  A frame of more than
+    ``nms_frames_max_candidates()`` candidates comes back empty.  One host read (ptr and candidates together)."""
+    _dev(label, "label", torch.int32), _dev(score, "score", torch.float32), _dev(keep, "keep", torch.int32)
+    _dev(corners, "corners", torch.float64), _dev(frame_ptr, "frame_ptr", torch.int64)
+    n = label.shape[0]
+    if label.dim() != 1 or score.shape != (n,) or keep.shape != (n,) or corners.shape != (n, 4, 2) or frame_ptr.dim() != 1 \
+            or frame_ptr.numel() < 1:
+        raise ValueError("shapes: label, score, keep [N], corners [N, 4, 2], frame_ptr [B + 1]")
+    label, score, keep, corners, frame_ptr = (t.contiguous() for t in (label, score, keep, corners, frame_ptr))
+    b = frame_ptr.numel() - 1
+    dev = label.device
+    out_dtype = torch.float64 if rotated else torch.float32
+    node = torch.empty(n, dtype=torch.int64, device=dev)
+    labels_out = torch.empty(n, dtype=torch.float64, device=dev)
+    scores_out = torch.empty(n, dtype=out_dtype, device=dev)
+    corners_out = torch.empty((n, 4, 2), dtype=out_dtype, device=dev)
+    meta = torch.empty(2 * b + 1, dtype=torch.int64, device=dev)
+    tmp = torch.empty(int(lib.rgnn_nms_frames_tmp_bytes(n, b)), dtype=torch.uint8, device=dev)
+    check(lib.rgnn_nms_frames(_ptr(label), _ptr(score), _ptr(keep), _ptr(corners), _ptr(frame_ptr), n, b, 1 if rotated else 0,
+                              float(iou_threshold), _ptr(tmp), _ptr(node), _ptr(labels_out), _ptr(scores_out), _ptr(corners_out),
+                              _ptr(meta), _stream()))
+    host = meta.cpu()
+    ptr, candidates = host[:b + 1], host[b + 1:]
+    k = int(ptr[b])
+    return node[:k], labels_out[:k], scores_out[:k], corners_out[:k], ptr, candidates
+
+
 # ---- evaluation: ground truth, duplicate removal, point IoU (csrc/postprocess.hip, csrc/evaluate.hip) ----------------
 def decode_ground_truth(labels: torch.Tensor, boxes: torch.Tensor, pos: torch.Tensor, nn_index: Optional[torch.Tensor],
                         bg_index: int, invariance: int):

@@ -8,8 +8,8 @@ The E(n)-invariant box representation needs every point's nearest neighbour: the
 (``ops.knn_graph``) instead of sklearn + a dense N x N ``toarray()`` (postprocessing.py:233-237).
 
 The evaluation half: ``GroundTruthExtractor`` (ground-truth decode + duplicate removal, postprocessing.py:438-575),
-``Postprocessor.process`` over whole lists of frames (one decode launch per half, one duplicate-removal launch; only NMS
-runs frame by frame) and the point IoU of ``utils/math.py:176-211`` (``point_iou``, ``point_iou_batched``) on
+``Postprocessor.process`` over whole lists of frames (one decode launch per half, one duplicate-removal launch, one
+segmented NMS: ``BoxSuppressor.apply_nms_frames`` -> ``Detections``) and the point IoU of ``utils/math.py:176-211`` (``point_iou``, ``point_iou_batched``) on
 ``rgnn_decode_ground_truth`` / ``rgnn_remove_duplicate_boxes`` / ``rgnn_point_iou``.
 """
 from __future__ import annotations
@@ -163,8 +163,13 @@ class BoxSuppressor:
     @classmethod
     def apply_nms(cls, bounding_boxes: BoundingBoxes, box_scores: torch.Tensor, box_labels: torch.Tensor, iou_nms: float):
         """-> (boxes kept, their scores [M', 1], their labels [M', 1]), by descending score like the reference."""
+        return cls._apply_nms_ids(bounding_boxes, box_scores, box_labels, iou_nms)[:3]
+
+    @classmethod
+    def _apply_nms_ids(cls, bounding_boxes: BoundingBoxes, box_scores: torch.Tensor, box_labels: torch.Tensor, iou_nms: float):
+        """``apply_nms`` and the ids kept (int64, positions in ``bounding_boxes``)."""
         if len(bounding_boxes) == 0:
-            return bounding_boxes, box_scores, box_labels
+            return bounding_boxes, box_scores, box_labels, torch.empty(0, dtype=torch.int64, device=box_scores.device)
         corners = bounding_boxes.corners
         if bounding_boxes.is_rotated:
             _, mat = ops.box_representations(corners, two_point=False, rotated=True)
@@ -190,7 +195,64 @@ class BoxSuppressor:
             kept_boxes = BoundingBoxes(rebuilt, True)
             scores = s32.index_select(0, keep).view(-1, 1)
         labels = box_labels.reshape(-1).index_select(0, keep).view(-1, 1)
-        return kept_boxes, scores, labels
+        return kept_boxes, scores, labels, keep
+
+    @classmethod
+    def apply_nms_frames(cls, corners: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, keep: torch.Tensor, frame_ptr,
+                         iou_nms: float, aligned: bool) -> "Detections":
+        """``apply_nms`` for every frame of a batch at once, on the outputs of ``decode`` (corners f64 [N, 4, 2], scores f32
+        [N], labels int32 [N], keep int32 [N]) and the node offsets of the frames: the candidates of each frame (keep != 0),
+        its own shift of negative coordinates, its own score order and greedy pass -- bit for bit what ``apply_nms`` returns
+        for the frame alone -- in two launches and one host read per batch (``ops.nms_frames``).  A frame with more
+        candidates than the kernel takes goes through ``apply_nms`` after that read and is spliced in."""
+        ptr_dev = _cuda(frame_ptr, "frame_ptr", torch.int64).reshape(-1)
+        node, out_labels, out_scores, out_corners, ptr, candidates = ops.nms_frames(labels, scores, keep, corners, ptr_dev,
+                                                                                     iou_nms, rotated=not aligned)
+        det = Detections(out_corners, out_scores, out_labels, node, ptr, aligned)
+        oversize = torch.nonzero(candidates > ops.nms_frames_max_candidates()).view(-1).tolist()
+        if not oversize:
+            return det
+        bounds = ptr_dev.cpu().tolist()
+        parts, new_ptr = [], [0]
+        for f in range(len(det)):
+            a, b = int(ptr[f]), int(ptr[f + 1])
+            part = (out_corners[a:b], out_scores[a:b], out_labels[a:b], node[a:b])
+            if f in oversize:
+                lo, hi = bounds[f], bounds[f + 1]
+                idx = torch.nonzero(keep[lo:hi], as_tuple=False).view(-1)
+                boxes, sc, lb, ids = cls._apply_nms_ids(BoundingBoxes(corners[lo:hi].index_select(0, idx), aligned),
+                                                        scores[lo:hi].index_select(0, idx).to(torch.float64).view(-1, 1),
+                                                        labels[lo:hi].index_select(0, idx).to(torch.float64).view(-1, 1), iou_nms)
+                part = (boxes.corners, sc[:, 0], lb[:, 0], idx.index_select(0, ids) + lo)
+            parts.append(part)
+            new_ptr.append(new_ptr[-1] + part[0].shape[0])
+        cat = [torch.cat([p[i] for p in parts]) for i in range(4)]
+        return Detections(cat[0], cat[1], cat[2], cat[3], torch.tensor(new_ptr, dtype=torch.int64), aligned)
+
+
+class Detections:
+    """The suppressed detections of a batch of frames in HBM, packed frame after frame: ``corners`` [K, 4, 2], ``scores``
+    [K] (float64 for rotated boxes; float32 for aligned ones, whose corners are the reference's float32 rebuild),
+    ``labels`` float64 [K], ``node`` int64 [K] (node id in the batch) and ``ptr`` int64 [B + 1] (frame offsets in K, on
+    the host).  ``len()`` is the number of frames."""
+
+    def __init__(self, corners, scores, labels, node, ptr, aligned: bool):
+        self.corners, self.scores, self.labels, self.node, self.ptr = corners, scores, labels, node, ptr
+        self.is_aligned = aligned
+        self._bounds = ptr.tolist()
+
+    def __len__(self) -> int:
+        return len(self._bounds) - 1
+
+    def frame(self, f: int) -> Dict:
+        """{"boxes", "scores", "labels"} of frame f as views -- the detection dict of ``Postprocessor``.  A frame without
+        detections had no candidates: it gets the empty float64 tensors ``apply_nms`` hands back for an empty input."""
+        a, b = self._bounds[f], self._bounds[f + 1]
+        if a == b:
+            dev = self.labels.device
+            return {"boxes": BoundingBoxes(torch.empty((0, 4, 2), dtype=torch.float64, device=dev), self.is_aligned),
+                    "scores": torch.empty(0, dtype=torch.float64, device=dev), "labels": torch.empty(0, dtype=torch.float64, device=dev)}
+        return {"boxes": BoundingBoxes(self.corners[a:b], self.is_aligned), "scores": self.scores[a:b], "labels": self.labels[a:b]}
 
 
 class Postprocessor:
@@ -212,9 +274,7 @@ class Postprocessor:
         labels = label.index_select(0, idx).to(torch.float64).view(-1, 1)
         boxes, scores, labels = BoxSuppressor.apply_nms(boxes, scores, labels, config.iou_for_nms)
         detection = {"boxes": boxes, "scores": scores[:, 0], "labels": labels[:, 0]}
-        segmentation = {"pos": pos, "labels": label.to(torch.float64), "scores": score.to(torch.float64),
-                        "clutter_scores": prob[:, config.bg_index]}
-        return detection, segmentation
+        return detection, Postprocessor._segmentation(config, pos, prob, label, score)
 
     @staticmethod
     def process_one_ground_truth(pos, vel, raw_bb_ground_truth, raw_cls_ground_truth, bb_invariance: str, bg_index: int):
@@ -230,7 +290,7 @@ class Postprocessor:
     def process(self, config: PostProcessingConfiguration, raw_pos, raw_vel, predictions: Dict, ground_truth: Dict):
         """postprocessing.py:120-163 over lists of graphs (numpy, as ``Predictor.predict`` returns them, or CUDA tensors):
         -> (bb_pred, bb_ground_truth, cls_pred, cls_ground_truth), lists of dicts with the reference's keys.  One decode launch
-        per half over all graphs, one duplicate-removal launch; NMS frame by frame."""
+        per half over all graphs, one duplicate-removal launch, one segmented NMS (``apply_nms_frames``)."""
         raw_bb_pred = predictions.get("bounding_box_predictions")
         raw_cls_prob_pred = predictions.get("class_probability_prediction")
         raw_bb_gt = ground_truth.get("bounding_box_true")
@@ -250,15 +310,10 @@ class Postprocessor:
         labels_gt = _concat([_labels_column(c) for c in raw_cls_gt], "class_true", None)
         nn_index = _nearest_in_frames(pos, ptr) if config.bb_invariance == "en" else None
 
-        # predictions: one decode launch, suppression per graph
+        # predictions: one decode launch, one segmented suppression
         label, score, keep, corners = decode(cls_prob, bb_pred, pos, config, nn_index=nn_index)
-        aligned_pred = bb_pred.shape[1] == 4
-        bb_out, cls_out = [], []
-        for a, b in zip(ptr[:-1], ptr[1:]):
-            det, seg = Postprocessor._finish(config, pos[a:b], cls_prob[a:b], label[a:b], score[a:b], keep[a:b], corners[a:b],
-                                             aligned_pred)
-            bb_out.append(det)
-            cls_out.append(seg)
+        pairs = Postprocessor._finish_frames(config, pos, cls_prob, label, score, keep, corners, bb_pred.shape[1] == 4, ptr)
+        bb_out, cls_out = [p[0] for p in pairs], [p[1] for p in pairs]
 
         # ground truth: one decode launch, one duplicate-removal launch
         gt_corners, gt_labels, box_ptr = _ground_truth(labels_gt, bb_gt, pos, ptr, config.bb_invariance, config.bg_index, nn_index)
@@ -273,22 +328,46 @@ class Postprocessor:
         return bb_out, gt_out, cls_out, gt_seg
 
     @staticmethod
+    def _segmentation(config, pos, prob, label, score) -> Dict:
+        return {"pos": pos, "labels": label.to(torch.float64), "scores": score.to(torch.float64),
+                "clutter_scores": prob[:, config.bg_index]}
+
+    @staticmethod
+    def _finish_frames(config, pos, prob, label, score, keep, corners, aligned, bounds: List[int]):
+        """``_finish`` for the frames [bounds[f], bounds[f + 1]) of one decode: list of (detection, segmentation) dicts.  More
+        than one frame: one segmented suppression, the dicts are slices of its result.  A single frame stays on ``_finish``:
+        ``rgnn_nms`` spreads the frame's IoUs over the whole device, the segmented kernel gives a frame one work-group
+        (MEASUREMENTS.md row 3)."""
+        if len(bounds) <= 2:
+            return [Postprocessor._finish(config, pos[a:b], prob[a:b], label[a:b], score[a:b], keep[a:b], corners[a:b], aligned)
+                    for a, b in zip(bounds[:-1], bounds[1:])]
+        det = BoxSuppressor.apply_nms_frames(corners, score, label, keep, torch.tensor(bounds, dtype=torch.int64), config.iou_for_nms,
+                                             aligned)
+        seg = Postprocessor._segmentation(config, pos, prob, label, score)
+        return [(det.frame(f), {k: v[a:b] for k, v in seg.items()}) for f, (a, b) in enumerate(zip(bounds[:-1], bounds[1:]))]
+
+    @staticmethod
+    def detect_batch(config: PostProcessingConfiguration, pos, raw_bb_pred, raw_cls_prob_pred, ptr):
+        """Decode and segmented suppression of a whole batch (``Batch.ptr`` / ``FrameBatch.frame_ptr`` node offsets): three
+        launches (plus the neighbour search of the "en" boxes) and one host read, whatever the number of frames.
+        -> (``Detections``, the segmentation tensors of the batch: {"pos", "labels", "scores", "clutter_scores"} over all
+        nodes)."""
+        ptr_dev = _cuda(ptr, "ptr", torch.int64)
+        label, score, keep, corners = decode(raw_cls_prob_pred, raw_bb_pred, pos, config, frame_ptr=ptr_dev)
+        det = BoxSuppressor.apply_nms_frames(corners, score, label, keep, ptr_dev, config.iou_for_nms,
+                                             torch.as_tensor(raw_bb_pred).shape[1] == 4)
+        return det, Postprocessor._segmentation(config, _f32_cuda(pos, "pos"), _f32_cuda(raw_cls_prob_pred, "cls"), label, score)
+
+    @staticmethod
     def process_batch(config: PostProcessingConfiguration, pos, raw_bb_pred, raw_cls_prob_pred, ptr):
         """The same for a whole batch straight from the model (``Batch.ptr`` / ``FrameBatch.frame_ptr`` node offsets): ONE
-        decode launch over all nodes (nearest neighbours for the "en" boxes searched per frame), then suppression frame by
-        frame like ``Postprocessor.process`` (postprocessing.py:150-154).  -> list of (detection, segmentation) dicts."""
-        ptr_dev = torch.as_tensor(ptr, dtype=torch.int64)
-        if not ptr_dev.is_cuda:
-            ptr_dev = ptr_dev.cuda()
+        decode launch over all nodes (nearest neighbours for the "en" boxes searched per frame), then one segmented
+        suppression (postprocessing.py:150-154 for every frame at once).  -> list of (detection, segmentation) dicts."""
+        ptr_dev = _cuda(ptr, "ptr", torch.int64)
         label, score, keep, corners = decode(raw_cls_prob_pred, raw_bb_pred, pos, config, frame_ptr=ptr_dev)
         pos32, prob = _f32_cuda(pos, "pos"), _f32_cuda(raw_cls_prob_pred, "cls")
         aligned = torch.as_tensor(raw_bb_pred).shape[1] == 4
-        bounds = ptr_dev.cpu().tolist()
-        out = []
-        for a, b in zip(bounds[:-1], bounds[1:]):
-            out.append(Postprocessor._finish(config, pos32[a:b], prob[a:b], label[a:b], score[a:b], keep[a:b], corners[a:b],
-                                             aligned))
-        return out
+        return Postprocessor._finish_frames(config, pos32, prob, label, score, keep, corners, aligned, ptr_dev.cpu().tolist())
 
 
 # ---------------------------------------------------------------------------------------------------- evaluation half
