@@ -41,7 +41,7 @@ typedef void* rgnn_stream_t; /* hipStream_t */
 #define RGNN_STATUS_KNN_TOO_FEW_POINTS 1 /* a frame has n_f <= k: sklearn raises ValueError              */
 #define RGNN_STATUS_DOT_PRODUCT 2        /* graph_constructor/features.py:56,77,91 "Error in dot product" */
 #define RGNN_STATUS_TIME_INDEX_OVERFLOW 4 /* more distinct timestamps in a frame than the LDS table holds  */
-#define RGNN_STATUS_EDGE_COUNT_CHANGED 8 /* rgnn_radius_graph_fill_checked: rowptr[n] != the n_edges the caller sized for */
+#define RGNN_STATUS_EDGE_COUNT_CHANGED 8 /* rgnn_radius_graph_fill with status: rowptr[n] != the n_edges the caller sized for */
 #define RGNN_STATUS_NOT_SYMMETRIC 16     /* rgnn_csr_by_target_symmetric: an edge (s,t) without its twin (t,s)               */
 #define RGNN_STATUS_SPLITK_TIMEOUT 32    /* a dense launch gave up waiting for a partial tile of another work-group (see splitk_ws) */
 #define RGNN_STATUS_GT_OBJECT_TOO_LARGE 64   /* rgnn_create_gt_boxes: an object of more than rgnn_gt_object_cap() points; its rows are not written */
@@ -111,15 +111,13 @@ int64_t rgnn_grid_workspace_bytes(int64_t n, int64_t n_frames, int32_t dim);
 
 /* Bin the points of every frame into a uniform grid on the first two coordinates.
  *   cell_size > 0 : radius mode, cells no smaller than cell_size (3x3 neighbourhood covers radius r = cell_size)
- *   cell_size <= 0: kNN mode, cell edge chosen per frame for ~pts_per_cell points per cell             */
-int rgnn_grid_build(const rgnn_grid* g, double cell_size, double pts_per_cell, rgnn_stream_t stream);
-/* The same with a hint: max_frame_points > 0 = no frame of the batch holds more points than this (the caller's host copy of
- * the frame sizes).  Frames of moderate size are then binned by ONE launch -- one block per frame: bounding box, grid, cell
- * histogram, local scan, cell order -- instead of five; 0 = no promise (the general path).  Same cells either way. */
-int rgnn_grid_build_frames(const rgnn_grid* g, double cell_size, double pts_per_cell, int64_t max_frame_points,
-                           rgnn_stream_t stream);
+ *   cell_size <= 0: kNN mode, cell edge chosen per frame for ~pts_per_cell points per cell
+ * max_frame_points > 0: a hint -- no frame of the batch holds more points than this (the caller's host copy of the frame sizes).
+ * Frames of moderate size are then binned by ONE launch -- one block per frame: bounding box, grid, cell histogram, local scan,
+ * cell order -- instead of five; 0 = no promise (the general path).  Same cells either way. */
+int rgnn_grid_build(const rgnn_grid* g, double cell_size, double pts_per_cell, int64_t max_frame_points, rgnn_stream_t stream);
 /* Where the cell order (int32 [n]: point rows in grid-cell order) and its inverse (int32 [n]: position of point i in that
- * order) lie inside the workspace, as byte offsets: valid after rgnn_grid_build*, for as long as the workspace is. */
+ * order) lie inside the workspace, as byte offsets: valid after rgnn_grid_build, for as long as the workspace is. */
 int rgnn_grid_order_offsets(int64_t n, int64_t n_frames, int32_t dim, int64_t* order_offset /*host*/, int64_t* rank_offset /*host*/);
 
 /* Replayed (captured) steps: search + fill of a radius graph whose rows are already known -- `rowptr_committed` [n + 1] as
@@ -140,29 +138,26 @@ int rgnn_radius_graph_count(const rgnn_grid* g, double r, int32_t* deg /*[dev]*/
  * i, ascending.  Optionally also writes edge_index int64 [2,E] (row 0 = i "query", row 1 = j "neighbour",
  * graph.py:61-63 + dataset_creation.py:805); pass NULL to skip.  E = rowptr[n] is passed by the caller.
  * Must follow rgnn_radius_graph_count on the same grid (same workspace, same r): rows of up to 32 neighbours are copied
- * from what that pass found, denser rows are searched again. */
+ * from what that pass found, denser rows are searched again.
+ * status != NULL: the guarded form, for a caller that sized col / edge_index for an edge count it did NOT just read back (a
+ * captured HIP graph replayed on a resident batch): if rowptr[n] differs from n_edges the kernels write nothing -- the buffers
+ * keep their previous contents -- and status gets RGNN_STATUS_EDGE_COUNT_CHANGED.  NULL: unguarded. */
 int rgnn_radius_graph_fill(const rgnn_grid* g, double r, const int32_t* rowptr /*[dev]*/, int32_t* col /*[dev]*/,
                            int64_t* edge_index /*[dev] or NULL*/, int64_t n_edges, int32_t* tmp /*[dev] int32 [2*E]*/,
-                           rgnn_stream_t stream);
-/* The same pass for a caller that sized col / edge_index for an edge count it did NOT just read back (a captured HIP
- * graph replayed on a resident batch): if rowptr[n] differs from n_edges the kernels write nothing -- the buffers keep
- * their previous contents -- and status gets RGNN_STATUS_EDGE_COUNT_CHANGED. */
-int rgnn_radius_graph_fill_checked(const rgnn_grid* g, double r, const int32_t* rowptr /*[dev]*/, int32_t* col /*[dev]*/,
-                                   int64_t* edge_index /*[dev] or NULL*/, int64_t n_edges, int32_t* tmp /*[dev] int32 [2*E]*/,
-                                   int32_t* status /*[dev]*/, rgnn_stream_t stream);
+                           int32_t* status /*[dev] or NULL*/, rgnn_stream_t stream);
 /* Fill pass in ONE launch: finished rows (col ascending, edge_index) and, when relative_position != NULL, the edge attributes
  * [x_i - x_j, y_i - y_j] (graph.py:199-200; |.| of both when undirected != 0) as float [n_edges, 2] in edge order -- what
- * rgnn_radius_graph_fill / _fill_checked + rgnn_edge_features(relative_position) produce in three launches.  status != NULL:
+ * rgnn_radius_graph_fill + rgnn_edge_features(relative_position) produce in three launches.  status != NULL:
  * the guarded form (rowptr[n] must equal n_edges, else nothing is written and RGNN_STATUS_EDGE_COUNT_CHANGED is set).
  * tmp: [dev] int32 [n_edges] scratch. */
 int rgnn_radius_graph_rows(const rgnn_grid* g, double r, const int32_t* rowptr /*[dev]*/, int32_t* col /*[dev]*/,
                            int64_t* edge_index /*[dev] or NULL*/, int64_t n_edges, int32_t* tmp /*[dev]*/,
                            int32_t* status /*[dev] or NULL*/, float* relative_position /*[dev] or NULL*/, int32_t undirected,
                            rgnn_stream_t stream);
-/* Companion of the checked fill for everything DOWNSTREAM of it in a replayed step (CSR by target, chunk table, the edge
+/* Companion of the guarded fill for everything DOWNSTREAM of it in a replayed step (CSR by target, chunk table, the edge
  * kernels: all sized for n_edges): rowptr_new is what this replay's count + scan produced.  If rowptr_new[n] == n_edges it is
  * copied to rowptr_committed; otherwise rowptr_committed keeps the rows of the last replay that matched -- consistent with the
- * col / edge_index the checked fill then leaves untouched -- and status gets RGNN_STATUS_EDGE_COUNT_CHANGED (also when
+ * col / edge_index the guarded fill then leaves untouched -- and status gets RGNN_STATUS_EDGE_COUNT_CHANGED (also when
  * n_edges == 0).  Downstream kernels read rowptr_committed only, so a replay on modified points computes on the previous
  * graph instead of walking rows that no longer fit its buffers. */
 int rgnn_radius_rows_commit(const int32_t* rowptr_new /*[dev] n+1*/, int64_t n, int64_t n_edges,
@@ -171,26 +166,21 @@ int rgnn_radius_rows_commit(const int32_t* rowptr_new /*[dev] n+1*/, int64_t n, 
                             lengths travel with the rows (degree feature, lists of nodes with / without edges)*/,
                             rgnn_stream_t stream);
 
-/* k nearest neighbours excluding self; nbr int32 [n,k], each row ordered (distance asc, index asc).
- * Optionally writes edge_index int64 [2, n*k].  status gets RGNN_STATUS_KNN_TOO_FEW_POINTS if a frame has
- * <= k points (rows of that frame are filled with -1). */
-int rgnn_knn_graph(const rgnn_grid* g, int32_t k, int32_t* nbr /*[dev]*/, int64_t* edge_index /*[dev] or NULL*/,
-                   int32_t* status /*[dev]*/, rgnn_stream_t stream);
-
-/* rgnn_knn_graph with the write-out doing more (the team kernel has the query's coordinates and the neighbour ids in hand):
- * relative_position != NULL: float [n k, 2] edge attributes [x_i - x_j, y_i - y_j] in edge order (graph.py:199-200; |.| when
- * undirected != 0) -- what rgnn_edge_features(relative_position) computes in a launch of its own; degree_init != NULL: int32 [n]
- * preset with the out-degree k, the starting point of rgnn_undirected_degree_preset.  k <= 64 with either of them. */
-int rgnn_knn_graph_attrs(const rgnn_grid* g, int32_t k, int32_t* nbr, int64_t* edge_index, int32_t* status,
-                         float* relative_position, int32_t undirected, int32_t* degree_init, rgnn_stream_t stream);
-/* rgnn_knn_graph_attrs for a grid built by rgnn_grid_build_frames whose largest frame the caller knows: frames of at most 1 024
- * points (nuScenes-shaped sweeps: ~300) with 3 <= k <= 32 are searched by brute force per frame -- one wave per query, every point
- * of the frame evaluated with the KD-tree's float64 arithmetic, the k-th smallest distance found by a binary search over the
- * distance bits -- instead of the walk over the grid; same rows bit for bit (distance asc, index asc).  Anything else is handed
- * to rgnn_knn_graph_attrs.  Replaces sklearn kneighbors_graph behind graph_constructor/graph.py:52-66. */
-int rgnn_knn_graph_frames(const rgnn_grid* g, int32_t k, int64_t max_frame_points, int32_t* nbr, int64_t* edge_index, int32_t* status,
-                          float* relative_position, int32_t undirected, int32_t* degree_init, rgnn_stream_t stream);
-/* rgnn_undirected_degree for a `degree` array that already holds the out-degrees (rgnn_knn_graph_attrs): one launch. */
+/* k nearest neighbours excluding self; nbr int32 [n,k], each row ordered (distance asc, index asc).  Optionally writes edge_index
+ * int64 [2, n*k].  status gets RGNN_STATUS_KNN_TOO_FEW_POINTS if a frame has <= k points (rows of that frame are filled with -1).
+ * Replaces sklearn kneighbors_graph behind graph_constructor/graph.py:52-66.  The write-out can do more (the team kernel has the
+ * query's coordinates and the neighbour ids in hand), k <= 64 with either:
+ *   relative_position != NULL: float [n k, 2] edge attributes [x_i - x_j, y_i - y_j] in edge order (graph.py:199-200; |.| when
+ *     undirected != 0) -- what rgnn_edge_features(relative_position) computes in a launch of its own;
+ *   degree_init != NULL: int32 [n] preset with the out-degree k, the starting point of rgnn_undirected_degree_preset.
+ * max_frame_points > 0 (the hint rgnn_grid_build was given): frames of at most 1 024 points (nuScenes-shaped sweeps: ~300) with
+ * 3 <= k <= 32 are searched by brute force per frame -- one wave per query, every point of the frame evaluated with the KD-tree's
+ * float64 arithmetic, the k-th smallest distance found by a binary search over the distance bits -- instead of the walk over the
+ * grid; same rows bit for bit.  0, or anything else: the walk over the grid. */
+int rgnn_knn_graph(const rgnn_grid* g, int32_t k, int64_t max_frame_points, int32_t* nbr /*[dev]*/,
+                   int64_t* edge_index /*[dev] or NULL*/, int32_t* status /*[dev]*/, float* relative_position /*[dev] or NULL*/,
+                   int32_t undirected, int32_t* degree_init /*[dev] or NULL*/, rgnn_stream_t stream);
+/* rgnn_undirected_degree for a `degree` array that already holds the out-degrees (rgnn_knn_graph degree_init): one launch. */
 int rgnn_undirected_degree_preset(const int32_t* rowptr, const int32_t* col, int64_t n, int32_t* degree, rgnn_stream_t stream);
 /* The same number for the rows of a kNN search (nbr int32 [n, k]) from the CSR by target of its edge list (rgnn_csr_by_target:
  * rowptr_t / src_sorted / node_order): k + in-degree - |{in-edges (s -> i) with s in nbr[i]}|; no atomics, every target's own row
@@ -202,10 +192,8 @@ int rgnn_knn_degree_from_csr(const int32_t* rowptr_t, const int32_t* src_sorted,
 int rgnn_grid_cell_order(const rgnn_grid* g, int32_t* order /*[dev] [n]*/, rgnn_stream_t stream);
 
 /* Undirected degree: |{j : (i,j) in E or (j,i) in E}| for a CSR (rowptr,col) of the directed edges.
- * Replaces graph.py:93-96 (networkx Graph built from the dense adjacency).  in_deg_tmp: unused (kept for
- * ABI stability; may be NULL). */
-int rgnn_undirected_degree(const int32_t* rowptr, const int32_t* col, int64_t n, int32_t* in_deg_tmp,
-                           int32_t* degree_out, rgnn_stream_t stream);
+ * Replaces graph.py:93-96 (networkx Graph built from the dense adjacency). */
+int rgnn_undirected_degree(const int32_t* rowptr, const int32_t* col, int64_t n, int32_t* degree_out, rgnn_stream_t stream);
 
 /* Out-degree of every node as a rowptr: rowptr_s[p + 1] - rowptr_s[p] = number of edges whose SOURCE (edge_index row 0) is
  * the node at position p (position = rank[node], or the node id when rank is NULL).  With rgnn_split_targets this gives the
@@ -223,24 +211,21 @@ int rgnn_invert_permutation(const int32_t* order, int64_t n, int32_t* rank, rgnn
  * target_rank (optional, [dev] int32 [n]): segments are laid out in visiting order -- segment p holds the
  * edges whose target t has target_rank[t] == p -- so a kernel that visits targets in that order streams the
  * edge arrays contiguously.  NULL = natural order (segment t = target t).
+ * ordered == 0: without the stable order inside the segments -- the places the fill's atomics hand out are the result (perm and
+ * src_sorted agree with each other; which of a target's in-edges comes first varies from run to run).  For reductions that do not
+ * depend on that order -- max aggregation (torch-scatter max behind mpnn_layers.py:88): one pass over the edges less.
  * tmp: [dev] of rgnn_csr_by_target_tmp_bytes(n, E) bytes. */
 int64_t rgnn_csr_by_target_tmp_bytes(int64_t n, int64_t n_edges);
 int rgnn_csr_by_target(const int64_t* edge_index /*[dev] [2,E]*/, int64_t n, int64_t n_edges,
-                       const int32_t* target_rank, int32_t* rowptr_t, int32_t* src_sorted, int32_t* perm, void* tmp,
-                       rgnn_stream_t stream);
-/* The same without the stable order inside the segments: the places the fill's atomics hand out are the result (perm and
- * src_sorted agree with each other; which of a target's in-edges comes first varies from run to run).  For reductions that do not
- * depend on that order -- max aggregation (torch-scatter max behind mpnn_layers.py:88): one pass over the edges less. */
-int rgnn_csr_by_target_unordered(const int64_t* edge_index /*[dev] [2,E]*/, int64_t n, int64_t n_edges,
-                                 const int32_t* target_rank /*[dev] [n] or NULL*/, int32_t* rowptr_t, int32_t* src_sorted,
-                                 int32_t* perm, void* tmp, rgnn_stream_t stream);
+                       const int32_t* target_rank /*[dev] [n] or NULL*/, int32_t* rowptr_t, int32_t* src_sorted, int32_t* perm,
+                       void* tmp, int32_t ordered, rgnn_stream_t stream);
 
 /* rgnn_csr_by_target for a batch of frames whose graph has UNIFORM out-degree k with edges grouped by source (kNN graphs:
  * edge e = i k + j; n_edges == n k): ONE launch, one block per frame -- histogram, scan, fill and stable ordering are local to a
  * frame because its edges are a contiguous slice and all their targets lie inside it.  max_frame_points: the caller's largest
  * frame (<= 24 576).  Optionally leaves in_degree int32 [n] (node numbering) and frame_nonempty int32 [n_frames] (nodes with
  * incoming edges per frame) behind -- the inputs of rgnn_split_by_degree_frames.  perm_tmp: [dev] int32 [n_edges] scratch.
- * Same rowptr_t / src_sorted / perm as rgnn_csr_by_target. */
+ * Same rowptr_t / src_sorted / perm as rgnn_csr_by_target (ordered). */
 int rgnn_csr_by_target_frames(const int64_t* edge_index, int64_t n, int64_t n_edges, int64_t k, const int64_t* frame_ptr,
                               int64_t n_frames, int64_t max_frame_points, const int32_t* target_rank /*[dev] or NULL*/,
                               int32_t* rowptr_t, int32_t* src_sorted, int32_t* perm, int32_t* perm_tmp,
@@ -250,20 +235,17 @@ int rgnn_csr_by_target_frames(const int64_t* edge_index, int64_t n, int64_t n_ed
  * rowptr_src [dev] int32 [n+1] is that grouping (the search's rowptr).  A node's in-degree is then its row length and an
  * edge's place in its target's segment is the rank of its source in the target's row: no histogram, no atomics, no sort --
  * three small kernels instead of six.  Identical outputs to rgnn_csr_by_target (tests/test_gpu_graph.py).  If some (t,s) is
- * missing, *status (optional) gets RGNN_STATUS_NOT_SYMMETRIC and that edge is left out.  tmp: as above. */
+ * missing, *status (optional) gets RGNN_STATUS_NOT_SYMMETRIC and that edge is left out.  tmp: as above.
+ * With edges, exactly ONE of perm and own_edge is given (else RGNN_ERR_INVALID_ARGUMENT).  own_edge (r03) instead of perm: no
+ * twin search -- the slot of the in-edge (i -> t) receives the id of the OUT-edge (t -> i).  For callers whose edge attributes are
+ * antisymmetric under reversal -- relative_position in directed mode: attr(i -> t) = -attr(t -> i), exactly -- the target-ordered
+ * attributes are then -attr[own_edge[slot]].  SYMMETRY IS NOT CHECKED on that path (an edge (t -> i) without (i -> t) would
+ * silently appear as an in-edge with negated attributes; RGNN_STATUS_NOT_SYMMETRIC is never set for a missing twin): only for
+ * edge lists that are symmetric by construction -- the output of rgnn_radius_graph_fill. */
 int rgnn_csr_by_target_symmetric(const int64_t* edge_index /*[dev] [2,E]*/, const int32_t* rowptr_src, int64_t n,
                                  int64_t n_edges, const int32_t* target_rank, int32_t* rowptr_t, int32_t* src_sorted,
-                                 int32_t* perm, void* tmp, int32_t* status /*[dev] or NULL*/, rgnn_stream_t stream);
-/* rgnn_csr_by_target_symmetric without the twin search (r03): instead of perm (edge id of the in-edge at every slot) it writes
- * own_edge: the id of the OUT-edge (t -> i) at the slot of its twin (i -> t).  For callers whose edge attributes are
- * antisymmetric under reversal -- relative_position in directed mode: attr(i -> t) = -attr(t -> i), exactly -- the target-ordered
- * attributes are then -attr[own_edge[slot]] and the binary search per edge is not needed.
- * SYMMETRY IS NOT CHECKED on this path (no twin search: an edge (t -> i) without (i -> t) would silently appear as an in-edge
- * with negated attributes; RGNN_STATUS_NOT_SYMMETRIC is never set): only for edge lists that are symmetric by construction --
- * the output of rgnn_radius_graph_fill.  Anything else goes through rgnn_csr_by_target_symmetric, which checks. */
-int rgnn_csr_by_target_symmetric_own(const int64_t* edge_index, const int32_t* rowptr_src, int64_t n, int64_t n_edges,
-                                     const int32_t* target_rank, int32_t* rowptr_t, int32_t* src_sorted, int32_t* own_edge,
-                                     void* tmp, int32_t* status, rgnn_stream_t stream);
+                                 int32_t* perm /*[dev] or NULL*/, int32_t* own_edge /*[dev] or NULL*/, void* tmp,
+                                 int32_t* status /*[dev] or NULL*/, rgnn_stream_t stream);
 
 /* ================================================================ features
  * Edge feature codes, concatenated in list order (graph.py:139-223).                                  */
@@ -289,7 +271,7 @@ int rgnn_edge_features(const double* X, const double* V, const int64_t* edge_ind
                        int32_t out_is_f64, int32_t* status /*[dev]*/, rgnn_stream_t stream);
 
 /* The same features for the REVERSED edges at the rows of a list: out[s] = features(E[1][e], E[0][e]) with e = reversed_of[s]
- * (int32 [n_rows]).  With reversed_of = the own_edge list of rgnn_csr_by_target_symmetric_own this is the attribute list in target
+ * (int32 [n_rows]).  With reversed_of = the own_edge list of rgnn_csr_by_target_symmetric this is the attribute list in target
  * order of a symmetric graph -- bit-identical to gathering every in-edge's own row (same arithmetic, same end points) -- without the
  * search for the twin's edge id.  Replaces the same reference lines as rgnn_edge_features (graph.py:139-223) plus the re-ordering that
  * torch_geometric's scatter makes unnecessary there. */
@@ -364,7 +346,7 @@ typedef struct rgnn_linear_args {
   /* Row subsets (all optional): tile row r works on matrix row row_index[r] of A1/A2/residual/out; the number of
    * rows is read from device memory (m_dev, with m an upper bound used for the launch geometry); accumulate: out +=
    * result (no col_stats with it).  Panels of col_stats that receive no rows are not written: zero the buffer first, or hand
-   * the launch's row count to rgnn_batchnorm_finalize_parts. */
+   * the launch's row count to rgnn_batchnorm_finalize (rows_a / rows_b). */
   const int32_t* row_index;
   const int64_t* m_dev;
   int32_t accumulate;
@@ -406,7 +388,7 @@ typedef struct rgnn_linear_args {
    *   a1_bound / a2_bound: [dev] bounds (RGNN_BOUND_SLOTS floats each, see below) holding an UPPER BOUND of |A1'| (A1 after a1_scale_shift / a1_relu) and of |A2|
    *     (a2_bound only when k2 > 0).  Elements beyond the bound overflow to infinity; a bound up to 2^19 above the tensor's
    *     typical magnitude costs no accuracy.  Producers: out_absmax of the launch that wrote the operand,
-   *     rgnn_mpnn_aggregate_flags' out_absmax, rgnn_batchnorm_bound for an operand behind a1_scale_shift.
+   *     rgnn_mpnn_aggregate's out_absmax, rgnn_batchnorm_finalize's out_bound for an operand behind a1_scale_shift.
    * out_absmax: [dev] bound (RGNN_BOUND_SLOTS floats), raised to max |out| over everything this launch stores (zero it first; LDS-DMA kernel
    *   only, either form: rgnn_linear_fwd returns RGNN_ERR_UNSUPPORTED if another kernel would take the launch). */
   const void* W_planes_f16;
@@ -473,37 +455,27 @@ int rgnn_tiny_mlp2(const float* A, int64_t lda, int32_t k0, const int32_t* row_i
 /* ================================================================ BatchNorm1d (gnn_models.py:71-73,126-128)
  * Training: combine col_stats (float64) -> batch mean / biased variance -> the apply table {mean_hi, g, t} (RGNN_AFFINE_ROWS);
  * running stats updated with momentum and the unbiased variance; num_batches_tracked += 1.
- * Eval (training == 0): the table from the running statistics, col_stats ignored. */
-int rgnn_batchnorm_finalize(const float* col_stats, int64_t panels, int64_t m, int32_t n, const float* gamma,
-                            const float* beta, float* running_mean, float* running_var,
-                            int64_t* num_batches_tracked, int32_t training, float momentum, float eps,
-                            float* scale_shift /*[RGNN_AFFINE_ROWS,n]*/, rgnn_stream_t stream);
-/* The same for a layer whose rows were produced by TWO row-subset launches (mpnn_layers.py:89-90 on the targets with and
- * without incoming edges), each with a col_stats buffer of its own: rows_a / rows_b ([dev], optional) are the m_dev row
- * counts of those launches; only the ceil(rows / 128) panels a launch really wrote are read, so the buffers need no zero fill.
- * stats_b may be NULL (one part). */
-int rgnn_batchnorm_finalize_parts(const float* stats_a, int64_t panels_a, const int64_t* rows_a /*[dev] or NULL*/,
-                                  const float* stats_b, int64_t panels_b, const int64_t* rows_b /*[dev] or NULL*/,
-                                  int64_t m, int32_t n, const float* gamma, const float* beta, float* running_mean,
-                                  float* running_var, int64_t* num_batches_tracked, int32_t training, float momentum,
-                                  float eps, float* scale_shift /*[RGNN_AFFINE_ROWS,n]*/, rgnn_stream_t stream);
-/* The same, additionally propagating a bound for the f16x2 dense form (rgnn_linear_args.a1_bound): in_bound [dev] (a bound, RGNN_BOUND_SLOTS floats) holds an upper
- * bound B of |x| over the matrix the statistics were taken of (the producing launches' out_absmax); out_bound ([dev] bound,
- * zeroed by the caller) receives max over the columns of |g| (B + |mean_hi|) + |t| -- an upper bound of |(x - mean_hi) g + t|, hence of
- * the ReLU of it.  stats_b / rows_* / the bounds may be NULL. */
-int rgnn_batchnorm_finalize_bound(const float* stats_a, int64_t panels_a, const int64_t* rows_a /*[dev] or NULL*/,
-                                  const float* stats_b, int64_t panels_b, const int64_t* rows_b /*[dev] or NULL*/,
-                                  int64_t m, int32_t n, const float* gamma, const float* beta, float* running_mean,
-                                  float* running_var, int64_t* num_batches_tracked, int32_t training, float momentum,
-                                  float eps, float* scale_shift /*[RGNN_AFFINE_ROWS,n]*/, const float* in_bound, float* out_bound,
-                                  rgnn_stream_t stream);
+ * Eval (training == 0): the table from the running statistics, col_stats ignored.
+ * The rows of a layer may come from TWO row-subset launches (mpnn_layers.py:89-90 on the targets with and without incoming
+ * edges), each with a col_stats buffer of its own: stats_b may be NULL (one part); rows_a / rows_b ([dev], optional) are the
+ * m_dev row counts of those launches -- only the ceil(rows / 128) panels a launch really wrote are read, so the buffers need no
+ * zero fill.  Bound for the f16x2 dense form (rgnn_linear_args.a1_bound; both optional, out_bound needs in_bound): in_bound [dev]
+ * (a bound, RGNN_BOUND_SLOTS floats) holds an upper bound B of |x| over the matrix the statistics were taken of (the producing
+ * launches' out_absmax); out_bound ([dev] bound, zeroed by the caller) receives max over the columns of
+ * |g| (B + |mean_hi|) + |t| -- an upper bound of |(x - mean_hi) g + t|, hence of the ReLU of it. */
+int rgnn_batchnorm_finalize(const float* stats_a, int64_t panels_a, const int64_t* rows_a /*[dev] or NULL*/,
+                            const float* stats_b /*or NULL*/, int64_t panels_b, const int64_t* rows_b /*[dev] or NULL*/,
+                            int64_t m, int32_t n, const float* gamma, const float* beta, float* running_mean,
+                            float* running_var, int64_t* num_batches_tracked, int32_t training, float momentum, float eps,
+                            float* scale_shift /*[RGNN_AFFINE_ROWS,n]*/, const float* in_bound /*or NULL*/,
+                            float* out_bound /*or NULL*/, rgnn_stream_t stream);
 /* Train-mode BatchNorm with statistics PER SEGMENT of rows -- segment f = rows [seg_ptr[f], seg_ptr[f + 1]), one segment per
  * radar frame of a batch.  The reference runs inference one frame per forward and never calls .eval() (evaluate.py:40,
  * postprocessor/inference.py:57-62, gnn/gnn_models.py:124-128): every frame is normalised with its own batch statistics; this
  * reproduces that in a batched launch.  table [dev] float [n_seg, RGNN_AFFINE_ROWS, n] receives the apply table of every segment; the running
  * statistics are walked through the segments in order (what a loop of single-frame forwards does), num_batches_tracked grows
  * by the number of non-empty segments.  seg_sums: [dev] scratch, double [n_seg, 2, n].  in_bound / out_bound: as in
- * rgnn_batchnorm_finalize_bound (optional). */
+ * rgnn_batchnorm_finalize (optional). */
 int rgnn_batchnorm_segments(const float* x, int64_t ldx, const int64_t* seg_ptr /*[dev] n_seg + 1*/, int64_t n_seg, int32_t n,
                             const float* gamma, const float* beta, float* running_mean, float* running_var,
                             int64_t* num_batches_tracked, float momentum, float eps, double* seg_sums, float* table,
@@ -557,55 +529,37 @@ int rgnn_scale_shift_act(const float* x, int64_t ldx, const float* scale_shift, 
  * `node_order` (with a CSR built with the matching `target_rank`) only changes the order in which targets are
  * processed (cache locality), never the result: segment p of the CSR belongs to target node_order[p].
  * Replaces MessagePassing.propagate (index_select gathers + cat + addmm + scatter) at
- * mpnn_layers.py:88,94-101 / :173,179-184. */
+ * mpnn_layers.py:88,94-101 / :173,179-184.
+ * flags: RGNN_MPNN_SKIP_EMPTY_ROWS -- rows of `out` that belong to targets without incoming edges may be left unwritten (callers
+ * that run the update only on the other rows -- rgnn_split_targets -- never read them; it saves their share of the output traffic).
+ * out_absmax ([dev] bound of RGNN_BOUND_SLOTS floats, zeroed by the caller; NULL = not wanted): the maximum of |out| over the rows
+ * written -- the bound the f16x2 dense form wants for its A2 operand (rgnn_linear_args.a2_bound).  The fused max kernel tracks it
+ * per lane at no measurable cost; other kernels are followed by one pass over `out`. */
 #define RGNN_AGGR_MAX 0
 #define RGNN_AGGR_MEAN 1
 #define RGNN_AGGR_ADD 2
+#define RGNN_MPNN_SKIP_EMPTY_ROWS 1
 int rgnn_mpnn_aggregate(const float* P, int64_t ldp, const float* p_bias, const float* Q, int64_t ldq,
                         const float* We /*[d, de], row stride ldwe*/, int64_t ldwe, const float* edge_attr_sorted,
                         int32_t de, const int32_t* rowptr_t, const int32_t* src_sorted,
                         const int32_t* node_order /*[dev] [n] visiting order of the targets, or NULL*/,
                         const int32_t* chunk_start /*[dev] from rgnn_mpnn_partition, or NULL*/, int32_t n_chunks, int64_t n,
-                        int32_t d, int32_t aggr, float* out, int64_t ldo, rgnn_stream_t stream);
-
-/* Same with options.  RGNN_MPNN_SKIP_EMPTY_ROWS: rows of `out` that belong to targets without incoming edges may be left
- * unwritten (callers that run the update only on the other rows -- rgnn_split_targets -- never read them; it saves their
- * share of the output traffic). */
-#define RGNN_MPNN_SKIP_EMPTY_ROWS 1
-int rgnn_mpnn_aggregate_flags(const float* P, int64_t ldp, const float* p_bias, const float* Q, int64_t ldq,
-                              const float* We, int64_t ldwe, const float* edge_attr_sorted, int32_t de,
-                              const int32_t* rowptr_t, const int32_t* src_sorted, const int32_t* node_order,
-                              const int32_t* chunk_start, int32_t n_chunks, int64_t n, int32_t d, int32_t aggr, float* out,
-                              int64_t ldo, int32_t flags, rgnn_stream_t stream);
-/* Same, additionally tracking out_absmax ([dev] bound of RGNN_BOUND_SLOTS floats, zeroed by the caller; NULL = not wanted): the maximum of |out|
- * over the rows written -- the bound the f16x2 dense form wants for its A2 operand (rgnn_linear_args.a2_bound).  The fused
- * max kernel tracks it per lane at no measurable cost; other kernels are followed by one pass over `out`. */
-int rgnn_mpnn_aggregate_absmax(const float* P, int64_t ldp, const float* p_bias, const float* Q, int64_t ldq,
-                               const float* We, int64_t ldwe, const float* edge_attr_sorted, int32_t de,
-                               const int32_t* rowptr_t, const int32_t* src_sorted, const int32_t* node_order,
-                               const int32_t* chunk_start, int32_t n_chunks, int64_t n, int32_t d, int32_t aggr, float* out,
-                               int64_t ldo, int32_t flags, float* out_absmax, rgnn_stream_t stream);
+                        int32_t d, int32_t aggr, float* out, int64_t ldo, int32_t flags, float* out_absmax /*[dev] or NULL*/,
+                        rgnn_stream_t stream);
 /* Max aggregation without a target term, recording the winners for the backward pass: arg_out uint16 [n, d] receives, per
  * target with incoming edges and channel, the index INSIDE the target's segment of the first edge that attains the maximum
  * (in-degrees must stay below 65 536).  Only the fused max kernel can record them (d % 8 == 0, 16-byte aligned rows, chunk
- * table given, de <= 8): *arg_written (host) says whether it ran -- if 0, out is complete but arg_out is untouched
- * (rgnn_mpnn_max_bwd then recomputes the winners). */
+ * table given, de <= 8): *arg_written (host, required) says what ran -- bit 0 = winners recorded (if clear, out is complete but
+ * arg_out is untouched and rgnn_mpnn_max_bwd recomputes the winners), bit 1 = max |out| raised into out_absmax (NULL = not
+ * wanted; over the rows written), so that the update GEMM of a TRAINING forward takes the f16x2 form like the inference one. */
 int rgnn_mpnn_aggregate_max_arg(const float* p_bias, const float* Q, int64_t ldq, const float* We, int64_t ldwe,
                                 const float* edge_attr_sorted, int32_t de, const int32_t* rowptr_t, const int32_t* src_sorted,
                                 const int32_t* node_order, const int32_t* chunk_start, int32_t n_chunks, int64_t n, int32_t d,
                                 float* out, int64_t ldo, uint16_t* arg_out, int32_t flags, int32_t* arg_written /*host*/,
-                                rgnn_stream_t stream);
-/* ... the same launch also tracking max |out| into out_absmax (a bound, RGNN_BOUND_SLOTS words; NULL: rgnn_mpnn_aggregate_max_arg),
- * so that the update GEMM of a TRAINING forward takes the f16x2 form like the inference one.  *arg_written: bit 0 = winners
- * recorded, bit 1 = max |out| tracked (over the rows written). */
-int rgnn_mpnn_aggregate_max_arg_absmax(const float* p_bias, const float* Q, int64_t ldq, const float* We, int64_t ldwe,
-                                       const float* edge_attr_sorted, int32_t de, const int32_t* rowptr_t, const int32_t* src_sorted,
-                                       const int32_t* node_order, const int32_t* chunk_start, int32_t n_chunks, int64_t n, int32_t d,
-                                       float* out, int64_t ldo, uint16_t* arg_out, int32_t flags, int32_t* arg_written /*host*/,
-                                       float* out_absmax, rgnn_stream_t stream);
+                                float* out_absmax /*[dev] or NULL*/, rgnn_stream_t stream);
 
 /* ---- window form of the max aggregation (mpnn_tiles.hip; what the folded layers run on graphs it pays for) ---------------------
- * The same sum as rgnn_mpnn_aggregate_absmax with aggr = max, P = NULL and de <= 8 (the folded layers the models ship), computed
+ * The same sum as rgnn_mpnn_aggregate with aggr = max, P = NULL and de <= 8 (the folded layers the models ship), computed
  * 32 edges x 32 channels at a time: the gathered Q values are the accumulator's initial value of v_mfma_f32_32x32x16_bf16 and
  * W_e z_e comes from the matrix pipe, z and W_e each split exactly into three bf16 terms (six products, fp32 accumulate:
  * ~2^-22 |z||w| from the fp32 chain of the per-edge kernel -- a frame's low bits therefore depend on which kernel its batch's
@@ -620,28 +574,24 @@ int rgnn_mpnn_aggregate_max_arg_absmax(const float* p_bias, const float* Q, int6
  *         (rowptr_t / src_sorted / node_order as for rgnn_mpnn_aggregate); once per graph, shared by all layers; holds the ticket
  *         counters and a weight scratch: ONE LAUNCH AT A TIME PER PLAN (two streams need two plans).
  * Returns RGNN_ERR_UNSUPPORTED for de > 8, d > 2048, n >= 2^24, Q rows not 16-byte aligned (ldq % 4, base address), rows of
- * 2^24 bytes or more, matrices or a plan of 2 GiB or more: the caller then takes rgnn_mpnn_aggregate_absmax
+ * 2^24 bytes or more, matrices or a plan of 2 GiB or more: the caller then takes rgnn_mpnn_aggregate
  * (radargnn_amd/gnn/mpnn_layers.py mirrors these limits).
- * flags / out_absmax as for rgnn_mpnn_aggregate_absmax.  Matches gnn/mpnn_layers.py:94-101 + torch-scatter max (hoisted form). */
+ * flags / out_absmax as for rgnn_mpnn_aggregate.  Matches gnn/mpnn_layers.py:94-101 + torch-scatter max (hoisted form).
+ * wplanes: the kernel's operand image of one layer's weights -- per 32-channel tile the three bf16 terms of W_e [d, de <= 8] and the
+ * bias -- depends on the weights only.  NULL: built into the plan's scratch in front of the launch (5 us); a caller that keeps it
+ * per weight version builds it once with rgnn_mpnn_win_wplanes ([dev] rgnn_mpnn_win_wplanes_bytes(d) bytes, 16-byte aligned) and
+ * passes it with the SAME We / p_bias (the per-target kernel still reads them). */
 int64_t rgnn_mpnn_win_plan_ints(int64_t n, int64_t n_edges);
 /* diagnostics: the words of a built plan that hold the number of targets left to the per-target kernel / of windows made */
 void rgnn_mpnn_win_plan_counters(int64_t n, int64_t n_edges, int64_t* leftover_word /*host*/, int64_t* windows_word /*host*/);
 int rgnn_mpnn_win_plan(const int32_t* rowptr_t, const int32_t* src_sorted, const int32_t* node_order, int64_t n, int64_t n_edges,
                        int32_t* plan, rgnn_stream_t stream);
+int64_t rgnn_mpnn_win_wplanes_bytes(int32_t d);
+int rgnn_mpnn_win_wplanes(const float* We, int64_t ldwe, int32_t de, int32_t d, const float* p_bias, void* planes, rgnn_stream_t stream);
 int rgnn_mpnn_aggregate_win(const float* p_bias, const float* Q, int64_t ldq, const float* We, int64_t ldwe,
                             const float* edge_attr_sorted, int32_t de, const int32_t* rowptr_t, const int32_t* src_sorted,
                             const int32_t* node_order, int32_t* plan, int64_t n, int64_t n_edges, int32_t d, float* out, int64_t ldo,
-                            int32_t flags, float* out_absmax, rgnn_stream_t stream);
-/* The kernel's operand image of one layer's weights -- per 32-channel tile the three bf16 terms of W_e [d, de <= 8] and the bias --
- * depends on the weights only.  rgnn_mpnn_aggregate_win builds it into the plan's scratch in front of every launch (5 us);
- * a caller that keeps it per weight version builds it once with rgnn_mpnn_win_wplanes ([dev] rgnn_mpnn_win_wplanes_bytes(d) bytes,
- * 16-byte aligned) and calls rgnn_mpnn_aggregate_win_planes with the SAME We / p_bias (the per-target kernel still reads them). */
-int64_t rgnn_mpnn_win_wplanes_bytes(int32_t d);
-int rgnn_mpnn_win_wplanes(const float* We, int64_t ldwe, int32_t de, int32_t d, const float* p_bias, void* planes, rgnn_stream_t stream);
-int rgnn_mpnn_aggregate_win_planes(const float* p_bias, const float* Q, int64_t ldq, const float* We, int64_t ldwe,
-                                   const float* edge_attr_sorted, int32_t de, const int32_t* rowptr_t, const int32_t* src_sorted,
-                                   const int32_t* node_order, int32_t* plan, int64_t n, int64_t n_edges, int32_t d, float* out,
-                                   int64_t ldo, int32_t flags, float* out_absmax, const void* wplanes, rgnn_stream_t stream);
+                            int32_t flags, float* out_absmax, const void* wplanes /*[dev] or NULL*/, rgnn_stream_t stream);
 
 /* Targets without incoming edges, in visiting order: list[0..count) = node ids (node_order[p] or p) of the empty CSR
  * segments; count is written to device memory (int64).  Deterministic (scan based).  flags_tmp: int32 [n],
@@ -850,26 +800,20 @@ int rgnn_confusion_matrix(const double* y_true, const double* y_pred, int64_t n,
 int rgnn_relu_bwd(const float* dy, const float* y, float* dx, int64_t count, rgnn_stream_t stream);
 
 /* Train-mode BatchNorm1d backward, reduction half: per 128-row panel the column sums of g and g*h, where
- * g = dy (y == NULL) or (y > 0 ? dy : 0) (BatchNorm followed by the fused ReLU, y = its output) and h = the
- * BatchNorm input.  partial: float [panels, 2, n], panels = rgnn_linear_stat_panels(m). */
-int rgnn_bn_bwd_stats(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* h, int64_t ldh, int64_t m,
-                      int32_t n, float* partial, rgnn_stream_t stream);
-
+ * g = dy (no ReLU: y == NULL and table == NULL) or dy masked by the fused ReLU that followed, and h = the BatchNorm input.  The
+ * mask is y > 0 (y = the ReLU's output) or, with table ([RGNN_AFFINE_ROWS, n] of rgnn_batchnorm_finalize, the forward pass's apply
+ * table), recomputed as fmaf(h - mean_hi, g, t) > 0 -- the bits of y as rgnn_scale_shift_act (or the A-operand path of
+ * rgnn_linear_fwd) produced them; a quarter to a third fewer bytes per pass.
+ * partial: float [panels, 2, n], panels = rgnn_linear_stat_panels(m). */
+int rgnn_bn_bwd_stats(const float* dy, int64_t lddy, const float* y /*or NULL*/, int64_t ldy, const float* table /*or NULL*/,
+                      const float* h, int64_t ldh, int64_t m, int32_t n, float* partial, rgnn_stream_t stream);
 /* ... elementwise half: dx = A[c] g + B[c] h + C[c], coef = [A | B | C] (3 n floats) with
- * A = gamma rstd, B = -gamma rstd^2 S/m, C = -gamma rstd sum(g)/m + gamma rstd^2 mean S/m, S = sum g xhat. */
-int rgnn_bn_bwd_apply(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* h, int64_t ldh,
-                      const float* coef, int64_t m, int32_t n, float* dx, int64_t lddx, rgnn_stream_t stream);
-/* ... also raising max |dx| into dx_absmax (a bound, RGNN_BOUND_SLOTS words zeroed by the caller; NULL: rgnn_bn_bwd_apply): the dgrad
- * launches that read dx then take the f16x2 form. */
-/* Both halves with the ReLU mask recomputed from h and the forward pass's apply table instead of read from y: table =
- * [RGNN_AFFINE_ROWS, n] of rgnn_batchnorm_finalize*, mask = fmaf(h - mean_hi, g, t) > 0 -- the bits of y as rgnn_scale_shift_act
- * (or the A-operand path of rgnn_linear_fwd) produced them; a quarter to a third fewer bytes per pass.  table NULL: y as above. */
-int rgnn_bn_bwd_stats_table(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* table, const float* h, int64_t ldh,
-                            int64_t m, int32_t n, float* partial, rgnn_stream_t stream);
-int rgnn_bn_bwd_apply_table(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* table, const float* h, int64_t ldh,
-                            const float* coef, int64_t m, int32_t n, float* dx, int64_t lddx, float* dx_absmax, rgnn_stream_t stream);
-int rgnn_bn_bwd_apply_absmax(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* h, int64_t ldh,
-                             const float* coef, int64_t m, int32_t n, float* dx, int64_t lddx, float* dx_absmax, rgnn_stream_t stream);
+ * A = gamma rstd, B = -gamma rstd^2 S/m, C = -gamma rstd sum(g)/m + gamma rstd^2 mean S/m, S = sum g xhat; y / table as above.
+ * dx_absmax (a bound, RGNN_BOUND_SLOTS words zeroed by the caller; NULL = not wanted) is raised to max |dx|: the dgrad launches
+ * that read dx then take the f16x2 form. */
+int rgnn_bn_bwd_apply(const float* dy, int64_t lddy, const float* y /*or NULL*/, int64_t ldy, const float* table /*or NULL*/,
+                      const float* h, int64_t ldh, const float* coef, int64_t m, int32_t n, float* dx, int64_t lddx,
+                      float* dx_absmax /*or NULL*/, rgnn_stream_t stream);
 /* The [3, n] coefficients of rgnn_bn_bwd_apply plus d gamma / d beta in one launch (float64 inside): from the forward column
  * statistics of the layer input (fwd_stats [panels_f, RGNN_STAT_ROWS, n], use_batch = 1) or the running statistics (use_batch = 0) and the
  * partial sums of rgnn_bn_bwd_stats (bwd_part [panels_b, 2, n]).  dgamma / dbeta may be NULL. */
@@ -888,21 +832,15 @@ int rgnn_segment_reduce_bwd(const float* dM, int64_t lddm, const float* rows, in
  * scanning their target's arg row).  Per sorted edge e: tgt_sorted[e] its target node, eloc_sorted[e] its index inside the
  * target's segment; per out-edge j of the source CSR: tloc[j] = eloc_sorted[tpos[j]].  arg: uint16 [n, d], the index (inside
  * the segment) of the edge that won channel c of target t -- recorded by the forward pass (arg_is_valid = 1) or recomputed
- * here from Q / W_e / the attributes (0).  dwe_partial: float [rgnn_mpnn_bwd_slots(n), d, de]. */
+ * here from Q / W_e / the attributes (0).  dwe_partial: float [rgnn_mpnn_bwd_slots(n), d, de].  dq_absmax (a bound; NULL = not
+ * wanted) is raised to max |dQ|. */
 int32_t rgnn_mpnn_max_bwd_supported(int32_t d, int32_t de);
 int rgnn_mpnn_max_bwd(const float* dM, int64_t lddm, const float* Q, int64_t ldq, const float* We, int64_t ldwe,
                       const float* edge_attr_sorted, int32_t de, const int32_t* rowptr_t, const int32_t* src_sorted,
                       const int32_t* tgt_sorted, const int32_t* eloc_sorted, const int32_t* node_order, int64_t n, int32_t d,
                       const int32_t* rowptr_s, const int32_t* tnode, const int32_t* tloc, int64_t n_edges, uint16_t* arg,
                       int32_t arg_is_valid, float* dwe_partial, float* dQ, int64_t lddq, float* d_edge_attr, float* dWe,
-                      rgnn_stream_t stream);
-/* ... also raising max |dQ| into dq_absmax (a bound; NULL: rgnn_mpnn_max_bwd). */
-int rgnn_mpnn_max_bwd_absmax(const float* dM, int64_t lddm, const float* Q, int64_t ldq, const float* We, int64_t ldwe,
-                             const float* edge_attr_sorted, int32_t de, const int32_t* rowptr_t, const int32_t* src_sorted,
-                             const int32_t* tgt_sorted, const int32_t* eloc_sorted, const int32_t* node_order, int64_t n, int32_t d,
-                             const int32_t* rowptr_s, const int32_t* tnode, const int32_t* tloc, int64_t n_edges, uint16_t* arg,
-                             int32_t arg_is_valid, float* dwe_partial, float* dQ, int64_t lddq, float* d_edge_attr, float* dWe,
-                             float* dq_absmax, rgnn_stream_t stream);
+                      float* dq_absmax /*or NULL*/, rgnn_stream_t stream);
 
 /* Weight gradient of a dense layer: dW[n, k] = sum_m G[m, n] * [A1 | A2][m, k] (G = gradient of the layer output after
  * the activation mask, A = the layer input), fp32 MFMA, reduction over the rows split into
@@ -919,19 +857,16 @@ int rgnn_linear_wgrad(const float* G, int64_t ldg, const float* A1, int64_t lda1
  * with_ones appends a column of ones to the input, so dW[:, k1 + k2] is the bias gradient (column sums of G over the same
  * rows).  partial: float [rgnn_wgrad_slabs(m, n, k1, k2, with_ones), n, k1 + k2 + with_ones]; dW [n, k1 + k2 + with_ones]
  * row-major.  Deterministic (slab partials summed by a second kernel, no atomics).  m = 0: dW is zeroed (the sum over nothing;
- * G / A may be NULL then). */
+ * G / A may be NULL then).
+ * The f16x2 form when every operand block comes with a bound (g_bound, a1_bound if k1 > 0, a2_bound if k2 > 0: arrays of
+ * RGNN_BOUND_SLOTS floats bounding |G| / |A1| / |A2| over the rows read): both operands pre-scaled by exact powers of two, split into
+ * two f16 terms, three MFMA products (l h', h l', h h') -- the forward kernels' f16x2 arithmetic; the column of ones is carried as
+ * 2^14 after the pre-scale.  Any bound NULL: the bf16x3 form. */
 int32_t rgnn_wgrad_slabs(int64_t m, int32_t n, int32_t k1, int32_t k2, int32_t with_ones);
 int rgnn_wgrad(const float* G, int64_t ldg, int32_t n, const float* A1, int64_t lda1, int32_t k1, const float* A2, int64_t lda2,
                int32_t k2, int32_t with_ones, int64_t m, const int32_t* row_index /*[dev] or NULL*/,
-               const int64_t* m_dev /*[dev] or NULL*/, float* partial, float* dW, rgnn_stream_t stream);
-/* ... in the f16x2 form when every operand block comes with a bound (g_bound, a1_bound if k1 > 0, a2_bound if k2 > 0: arrays of
- * RGNN_BOUND_SLOTS floats bounding |G| / |A1| / |A2| over the rows read): both operands pre-scaled by exact powers of two, split into
- * two f16 terms, three MFMA products (l h', h l', h h') -- the forward kernels' f16x2 arithmetic; the column of ones is carried as
- * 2^14 after the pre-scale.  Any bound NULL: the bf16x3 form of rgnn_wgrad. */
-int rgnn_wgrad_bounds(const float* G, int64_t ldg, int32_t n, const float* A1, int64_t lda1, int32_t k1, const float* A2, int64_t lda2,
-                      int32_t k2, int32_t with_ones, int64_t m, const int32_t* row_index /*[dev] or NULL*/,
-                      const int64_t* m_dev /*[dev] or NULL*/, const float* g_bound, const float* a1_bound, const float* a2_bound,
-                      float* partial, float* dW, rgnn_stream_t stream);
+               const int64_t* m_dev /*[dev] or NULL*/, const float* g_bound /*or NULL*/, const float* a1_bound /*or NULL*/,
+               const float* a2_bound /*or NULL*/, float* partial, float* dW, rgnn_stream_t stream);
 
 /* Backward of rgnn_mpnn_aggregate without its target term: M[t] = aggr_{e -> t}(Q[s_e] + W_e a_e) (0 for empty
  * segments).  max: the gradient of (t, c) goes to the first edge attaining the maximum (torch-scatter arg_out).

@@ -48,33 +48,27 @@ SIGNATURES = {
     "rgnn_scan_tmp_bytes": (c_i64, [c_i64]),
     "rgnn_exclusive_scan_i32": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "rgnn_grid_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
-    "rgnn_grid_build": (c_i32, [C.POINTER(RgnnGrid), c_f64, c_f64, c_vp]),
-    "rgnn_grid_build_frames": (c_i32, [C.POINTER(RgnnGrid), c_f64, c_f64, c_i64, c_vp]),
+    "rgnn_grid_build": (c_i32, [C.POINTER(RgnnGrid), c_f64, c_f64, c_i64, c_vp]),
     "rgnn_grid_order_offsets": (c_i32, [c_i64, c_i64, c_i32, C.POINTER(c_i64), C.POINTER(c_i64)]),
     "rgnn_radius_graph_count": (c_i32, [C.POINTER(RgnnGrid), c_f64, c_vp, c_vp]),
-    "rgnn_radius_graph_fill": (c_i32, [C.POINTER(RgnnGrid), c_f64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
-    "rgnn_radius_graph_fill_checked": (c_i32, [C.POINTER(RgnnGrid), c_f64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "rgnn_radius_graph_fill": (c_i32, [C.POINTER(RgnnGrid), c_f64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "rgnn_radius_graph_rows": (c_i32, [C.POINTER(RgnnGrid), c_f64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "rgnn_radius_graph_rows_direct": (c_i32, [C.POINTER(RgnnGrid), c_f64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "rgnn_radius_rows_commit": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "rgnn_knn_graph": (c_i32, [C.POINTER(RgnnGrid), c_i32, c_vp, c_vp, c_vp, c_vp]),
-    "rgnn_knn_graph_attrs": (c_i32, [C.POINTER(RgnnGrid), c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
-    "rgnn_knn_graph_frames": (c_i32, [C.POINTER(RgnnGrid), c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "rgnn_knn_graph": (c_i32, [C.POINTER(RgnnGrid), c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "rgnn_knn_degree_from_csr": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "rgnn_undirected_degree_preset": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "rgnn_grid_cell_order": (c_i32, [C.POINTER(RgnnGrid), c_vp, c_vp]),
-    "rgnn_undirected_degree": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "rgnn_undirected_degree": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "rgnn_csr_by_target_tmp_bytes": (c_i64, [c_i64, c_i64]),
     "rgnn_invert_permutation": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "rgnn_source_rowptr": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
-    "rgnn_csr_by_target": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "rgnn_csr_by_target_unordered": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_csr_by_target": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "rgnn_csr_by_target_frames": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "rgnn_csr_by_target_symmetric": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_csr_by_target_symmetric": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rgnn_embed3_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "rgnn_embed3": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_i64,
                             c_vp, c_vp]),
-    "rgnn_csr_by_target_symmetric_own": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rgnn_edge_features": (c_i32, [c_vp, c_vp, c_vp, c_i64, C.POINTER(c_i32), c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),
     "rgnn_edge_features_reversed": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, C.POINTER(c_i32), c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),
     "rgnn_node_features": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.POINTER(c_i32), c_i32, c_vp, c_i32, c_vp]),
@@ -97,12 +91,8 @@ SIGNATURES = {
     "rgnn_linear_split_weights": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rgnn_tiny_mlp2": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp,
                        c_i64, c_vp]),
-    "rgnn_batchnorm_finalize": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_f32,
-                                        c_vp, c_vp]),
-    "rgnn_batchnorm_finalize_parts": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32,
-                                              c_f32, c_f32, c_vp, c_vp]),
-    "rgnn_batchnorm_finalize_bound": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32,
-                                              c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_batchnorm_finalize": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_f32,
+                                        c_f32, c_vp, c_vp, c_vp, c_vp]),
     "rgnn_batchnorm_segments": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_vp, c_vp,
                                         c_vp, c_vp, c_vp]),
     "rgnn_batchnorm_act_segments": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_i32, c_vp,
@@ -114,25 +104,17 @@ SIGNATURES = {
     "rgnn_scale_shift_act_segments": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "rgnn_column_stats": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
     "rgnn_scale_shift_act": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp]),
-    "rgnn_mpnn_aggregate": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
-                                    c_i64, c_i32, c_i32, c_vp, c_i64, c_vp]),
-    "rgnn_mpnn_aggregate_flags": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
-                                          c_i64, c_i32, c_i32, c_vp, c_i64, c_i32, c_vp]),
-    "rgnn_mpnn_aggregate_absmax": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
-                                           c_i64, c_i32, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp]),
+    "rgnn_mpnn_aggregate": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64,
+                                    c_i32, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "rgnn_mpnn_aggregate_max_arg": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32,
-                                             c_vp, c_i64, c_vp, c_i32, C.POINTER(c_i32), c_vp]),
-    "rgnn_mpnn_aggregate_max_arg_absmax": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32,
-                                                    c_vp, c_i64, c_vp, c_i32, C.POINTER(c_i32), c_vp, c_vp]),
+                                            c_vp, c_i64, c_vp, c_i32, C.POINTER(c_i32), c_vp, c_vp]),
     "rgnn_mpnn_win_plan_ints": (c_i64, [c_i64, c_i64]),
     "rgnn_mpnn_win_plan_counters": (None, [c_i64, c_i64, C.POINTER(c_i64), C.POINTER(c_i64)]),
     "rgnn_mpnn_win_plan": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "rgnn_mpnn_aggregate_win": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp,
-                                        c_i64, c_i32, c_vp, c_vp]),
+                                        c_i64, c_i32, c_vp, c_vp, c_vp]),
     "rgnn_mpnn_win_wplanes_bytes": (c_i64, [c_i32]),
     "rgnn_mpnn_win_wplanes": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
-    "rgnn_mpnn_aggregate_win_planes": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp,
-                                               c_i64, c_i32, c_vp, c_vp, c_vp]),
     "rgnn_empty_targets": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rgnn_split_targets": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rgnn_split_targets_by_node": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
@@ -146,27 +128,21 @@ SIGNATURES = {
     "rgnn_gather_rows_f32": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp]),
     "rgnn_softmax_rows": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
     "rgnn_relu_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp]),
-    "rgnn_bn_bwd_stats": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
-    "rgnn_bn_bwd_apply": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp]),
-    "rgnn_bn_bwd_stats_table": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
-    "rgnn_bn_bwd_apply_table": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp]),
-    "rgnn_bn_bwd_apply_absmax": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp]),
+    "rgnn_bn_bwd_stats": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
+    "rgnn_bn_bwd_apply": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp]),
     "rgnn_bn_bwd_coef": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_f32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rgnn_mpnn_aggregate_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32,
                                         c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "rgnn_mpnn_max_bwd_supported": (c_i32, [c_i32, c_i32]),
     "rgnn_mpnn_max_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp,
-                                   c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
-    "rgnn_mpnn_max_bwd_absmax": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp,
-                                          c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+                                  c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rgnn_mpnn_bwd_split": (c_i32, [c_i32]),
     "rgnn_segment_reduce_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "rgnn_linear_wgrad_slabs": (c_i32, [c_i64, c_i32, c_i32]),
     "rgnn_linear_wgrad": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "rgnn_wgrad_slabs": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32]),
-    "rgnn_wgrad": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "rgnn_wgrad_bounds": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                   c_vp, c_vp]),
+    "rgnn_wgrad": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                           c_vp, c_vp, c_vp]),
     "rgnn_mpnn_bwd_slots": (c_i64, [c_i64]),
     "rgnn_decode_predictions": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_i32, C.c_float, c_vp, c_i32,
                                         c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),

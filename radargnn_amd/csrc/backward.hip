@@ -942,13 +942,8 @@ extern "C" int rgnn_relu_bwd(const float* dy, const float* y, float* dx, int64_t
   return RGNN_OK;
 }
 
-extern "C" int rgnn_bn_bwd_stats(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* h, int64_t ldh,
-                                 int64_t m, int32_t n, float* partial, rgnn_stream_t stream) {
-  return rgnn_bn_bwd_stats_table(dy, lddy, y, ldy, nullptr, h, ldh, m, n, partial, stream);
-}
-
-extern "C" int rgnn_bn_bwd_stats_table(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* table, const float* h,
-                                       int64_t ldh, int64_t m, int32_t n, float* partial, rgnn_stream_t stream) {
+extern "C" int rgnn_bn_bwd_stats(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* table, const float* h,
+                                 int64_t ldh, int64_t m, int32_t n, float* partial, rgnn_stream_t stream) {
   if (m == 0 || n == 0) return RGNN_OK;
   RGNN_CHECK_ARG(dy && h && partial, "null pointers");
   const unsigned panels = (unsigned)((m + 127) / 128);
@@ -958,20 +953,9 @@ extern "C" int rgnn_bn_bwd_stats_table(const float* dy, int64_t lddy, const floa
   return RGNN_OK;
 }
 
-extern "C" int rgnn_bn_bwd_apply(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* h, int64_t ldh,
-                                 const float* coef, int64_t m, int32_t n, float* dx, int64_t lddx, rgnn_stream_t stream) {
-  return rgnn_bn_bwd_apply_table(dy, lddy, y, ldy, nullptr, h, ldh, coef, m, n, dx, lddx, nullptr, stream);
-}
-
-extern "C" int rgnn_bn_bwd_apply_absmax(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* h, int64_t ldh,
-                                        const float* coef, int64_t m, int32_t n, float* dx, int64_t lddx, float* dx_absmax,
-                                        rgnn_stream_t stream) {
-  return rgnn_bn_bwd_apply_table(dy, lddy, y, ldy, nullptr, h, ldh, coef, m, n, dx, lddx, dx_absmax, stream);
-}
-
-extern "C" int rgnn_bn_bwd_apply_table(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* table, const float* h,
-                                       int64_t ldh, const float* coef, int64_t m, int32_t n, float* dx, int64_t lddx,
-                                       float* dx_absmax, rgnn_stream_t stream) {
+extern "C" int rgnn_bn_bwd_apply(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* table, const float* h,
+                                 int64_t ldh, const float* coef, int64_t m, int32_t n, float* dx, int64_t lddx, float* dx_absmax,
+                                 rgnn_stream_t stream) {
   if (m == 0 || n == 0) return RGNN_OK;
   RGNN_CHECK_ARG(dy && h && coef && dx, "null pointers");
   const bool vec = n % 4 == 0 && lddy % 4 == 0 && ldh % 4 == 0 && lddx % 4 == 0 && (y == nullptr || ldy % 4 == 0) &&
@@ -1067,18 +1051,7 @@ extern "C" int rgnn_mpnn_max_bwd(const float* dM, int64_t lddm, const float* Q, 
                                  const int32_t* tgt_sorted, const int32_t* eloc_sorted, const int32_t* node_order, int64_t n,
                                  int32_t d, const int32_t* rowptr_s, const int32_t* tnode, const int32_t* tloc, int64_t n_edges,
                                  uint16_t* arg, int32_t arg_is_valid, float* dwe_partial, float* dQ, int64_t lddq,
-                                 float* d_edge_attr, float* dWe, rgnn_stream_t stream) {
-  return rgnn_mpnn_max_bwd_absmax(dM, lddm, Q, ldq, We, ldwe, edge_attr_sorted, de, rowptr_t, src_sorted, tgt_sorted, eloc_sorted,
-                                  node_order, n, d, rowptr_s, tnode, tloc, n_edges, arg, arg_is_valid, dwe_partial, dQ, lddq,
-                                  d_edge_attr, dWe, nullptr, stream);
-}
-
-extern "C" int rgnn_mpnn_max_bwd_absmax(const float* dM, int64_t lddm, const float* Q, int64_t ldq, const float* We, int64_t ldwe,
-                                        const float* edge_attr_sorted, int32_t de, const int32_t* rowptr_t, const int32_t* src_sorted,
-                                        const int32_t* tgt_sorted, const int32_t* eloc_sorted, const int32_t* node_order, int64_t n,
-                                        int32_t d, const int32_t* rowptr_s, const int32_t* tnode, const int32_t* tloc, int64_t n_edges,
-                                        uint16_t* arg, int32_t arg_is_valid, float* dwe_partial, float* dQ, int64_t lddq,
-                                        float* d_edge_attr, float* dWe, float* dq_absmax, rgnn_stream_t stream) {
+                                 float* d_edge_attr, float* dWe, float* dq_absmax, rgnn_stream_t stream) {
   if (n == 0 || d == 0) return RGNN_OK;
   RGNN_CHECK_ARG(rgnn_mpnn_max_bwd_supported(d, de), "needs d % 8 == 0, d <= 512, 1 <= de <= 8 (else rgnn_mpnn_aggregate_bwd)");
   RGNN_CHECK_ARG(dM && Q && We && edge_attr_sorted && rowptr_t && src_sorted && tgt_sorted && eloc_sorted && rowptr_s && tnode &&

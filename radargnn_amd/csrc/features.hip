@@ -441,7 +441,7 @@ extern "C" int rgnn_edge_features(const double* X, const double* V, const int64_
 }
 
 // Edge features of the REVERSED edges at the rows of a list: out[s] = features(E[1][e], E[0][e]), e = reversed_of[s].  For a symmetric
-// edge list whose CSR by target was built without the twin search (rgnn_csr_by_target_symmetric_own: own_edge[slot] = the out-edge
+// edge list whose CSR by target was built without the twin search (rgnn_csr_by_target_symmetric with own_edge: own_edge[slot] = the out-edge
 // (t -> i) at the slot of the in-edge (i -> t)) this IS the attribute list in target order -- the same arithmetic on the same end
 // points as the twin's own row, so bit-identical to gathering the twin's row -- without looking the twin up (a binary search per edge:
 // 179 us and 1.1 GB of reads on the 100 000-point cloud).

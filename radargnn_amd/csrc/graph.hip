@@ -1758,12 +1758,8 @@ static int check_grid(const rgnn_grid* g) {
   return RGNN_OK;
 }
 
-extern "C" int rgnn_grid_build(const rgnn_grid* g, double cell_size, double pts_per_cell, rgnn_stream_t stream) {
-  return rgnn_grid_build_frames(g, cell_size, pts_per_cell, 0, stream);
-}
-
-extern "C" int rgnn_grid_build_frames(const rgnn_grid* g, double cell_size, double pts_per_cell, int64_t max_frame_points,
-                                      rgnn_stream_t stream) {
+extern "C" int rgnn_grid_build(const rgnn_grid* g, double cell_size, double pts_per_cell, int64_t max_frame_points,
+                               rgnn_stream_t stream) {
   int rc = check_grid(g);
   if (rc) return rc;
   if (g->n == 0) return RGNN_OK;
@@ -1867,20 +1863,11 @@ extern "C" int rgnn_radius_graph_count(const rgnn_grid* g, double r, int32_t* de
   return launch_radius<false>(g, r, deg, nullptr, nullptr, nullptr, 0, nullptr, nullptr, stream);
 }
 
-extern "C" int rgnn_radius_graph_fill(const rgnn_grid* g, double r, const int32_t* rowptr, int32_t* col,
-                                      int64_t* edge_index, int64_t n_edges, int32_t* tmp, rgnn_stream_t stream) {
+// status NULL: the unguarded fill; given: rowptr[n] must equal n_edges or nothing is written (k_radius / k_rank_rows check it)
+extern "C" int rgnn_radius_graph_fill(const rgnn_grid* g, double r, const int32_t* rowptr, int32_t* col, int64_t* edge_index,
+                                      int64_t n_edges, int32_t* tmp, int32_t* status, rgnn_stream_t stream) {
   RGNN_CHECK_ARG(g && (g->n == 0 || (rowptr && (col || n_edges == 0))), "null rowptr/col");
-  if (n_edges == 0) return RGNN_OK;
-  RGNN_CHECK_ARG(tmp != nullptr, "null tmp (int32 [2 * n_edges])");
-  return launch_radius<true>(g, r, nullptr, rowptr, col, edge_index, n_edges, tmp, nullptr, stream);
-}
-
-extern "C" int rgnn_radius_graph_fill_checked(const rgnn_grid* g, double r, const int32_t* rowptr, int32_t* col,
-                                              int64_t* edge_index, int64_t n_edges, int32_t* tmp, int32_t* status,
-                                              rgnn_stream_t stream) {
-  RGNN_CHECK_ARG(g && (g->n == 0 || (rowptr && (col || n_edges == 0))), "null rowptr/col");
-  RGNN_CHECK_ARG(status != nullptr, "null status");
-  if (n_edges == 0 || g->n == 0) return RGNN_OK;
+  if (n_edges == 0 || (status != nullptr && g->n == 0)) return RGNN_OK;   // (as both forms did: the unguarded one has its grid checked below)
   RGNN_CHECK_ARG(tmp != nullptr, "null tmp (int32 [2 * n_edges])");
   return launch_radius<true>(g, r, nullptr, rowptr, col, edge_index, n_edges, tmp, status, stream);
 }
@@ -1959,24 +1946,22 @@ extern "C" int rgnn_radius_rows_commit(const int32_t* rowptr_new, int64_t n, int
   return RGNN_OK;
 }
 
-extern "C" int rgnn_knn_graph(const rgnn_grid* g, int32_t k, int32_t* nbr, int64_t* edge_index, int32_t* status,
-                              rgnn_stream_t stream) {
-  return rgnn_knn_graph_attrs(g, k, nbr, edge_index, status, nullptr, 0, nullptr, stream);
-}
+static int knn_grid_walk(const rgnn_grid* g, int32_t k, int32_t* nbr, int64_t* edge_index, int32_t* status,
+                         float* relative_position, int32_t undirected, int32_t* degree_init, rgnn_stream_t stream);
 
-extern "C" int rgnn_knn_graph_frames(const rgnn_grid* g, int32_t k, int64_t max_frame_points, int32_t* nbr, int64_t* edge_index,
-                                     int32_t* status, float* relative_position, int32_t undirected, int32_t* degree_init,
-                                     rgnn_stream_t stream) {
+extern "C" int rgnn_knn_graph(const rgnn_grid* g, int32_t k, int64_t max_frame_points, int32_t* nbr, int64_t* edge_index,
+                              int32_t* status, float* relative_position, int32_t undirected, int32_t* degree_init,
+                              rgnn_stream_t stream) {
   int rc = check_grid(g);
   if (rc) return rc;
   RGNN_CHECK_ARG(k >= 1, "k must be >= 1");
   if (g->n == 0) return RGNN_OK;
   RGNN_CHECK_ARG(nbr && status, "null outputs");
   static const int brute_max = RGNN_ENV("RGNN_KNN_FRAME_MAX") ? atoi(RGNN_ENV("RGNN_KNN_FRAME_MAX")) : 512;   // (1 000-point frames: 455 us against the grid walk's 280)
-  // small frames (the grid was built by rgnn_grid_build_frames: frames are contiguous slices of the cell-ordered arrays): brute
+  // small frames (the grid was built by rgnn_grid_build with the same hint: frames are contiguous slices of the cell-ordered arrays): brute
   // force per frame, one wave per query (k_knn_frame); anything else: the grid walk
   if (max_frame_points < 1 || max_frame_points > brute_max || max_frame_points > 1024 || k > KF_MAXK || k < 3 || (g->dim != 2 && g->dim != 4))
-    return rgnn_knn_graph_attrs(g, k, nbr, edge_index, status, relative_position, undirected, degree_init, stream);
+    return knn_grid_walk(g, k, nbr, edge_index, status, relative_position, undirected, degree_init, stream);
   GridView v = make_view(g->ws, g->n, g->n_frames, g->dim);
   hipStream_t s = (hipStream_t)stream;
   const int wpf = (int)((max_frame_points + KF_QPW - 1) / KF_QPW);
@@ -1995,13 +1980,9 @@ extern "C" int rgnn_knn_graph_frames(const rgnn_grid* g, int32_t k, int64_t max_
   return RGNN_OK;
 }
 
-extern "C" int rgnn_knn_graph_attrs(const rgnn_grid* g, int32_t k, int32_t* nbr, int64_t* edge_index, int32_t* status,
-                                    float* relative_position, int32_t undirected, int32_t* degree_init, rgnn_stream_t stream) {
-  int rc = check_grid(g);
-  if (rc) return rc;
-  RGNN_CHECK_ARG(k >= 1, "k must be >= 1");
-  if (g->n == 0) return RGNN_OK;
-  RGNN_CHECK_ARG(nbr && status, "null outputs");
+// the walk over the grid cells (the caller has checked the arguments and n > 0)
+static int knn_grid_walk(const rgnn_grid* g, int32_t k, int32_t* nbr, int64_t* edge_index, int32_t* status,
+                         float* relative_position, int32_t undirected, int32_t* degree_init, rgnn_stream_t stream) {
   const size_t lds = (size_t)k * KNN_THREADS * 12;
   if (lds > 160 * 1024) {
     rgnn_set_error("rgnn_knn_graph: k = %d needs %zu B of LDS per block (max 163840)", k, lds);
@@ -2065,12 +2046,12 @@ extern "C" int rgnn_grid_cell_order(const rgnn_grid* g, int32_t* order, rgnn_str
   return RGNN_OK;
 }
 
-extern "C" int rgnn_undirected_degree(const int32_t* rowptr, const int32_t* col, int64_t n, int32_t* in_deg_tmp,
-                                      int32_t* degree_out, rgnn_stream_t stream) {
+extern "C" int rgnn_undirected_degree(const int32_t* rowptr, const int32_t* col, int64_t n, int32_t* degree_out,
+                                      rgnn_stream_t stream) {
   RGNN_CHECK_ARG(n >= 0, "negative n");
   if (n == 0) return RGNN_OK;
   RGNN_CHECK_ARG(rowptr && degree_out, "null pointers");
-  // row-parallel, so E (= rowptr[n], device-side) is never needed on the host; in_deg_tmp is no longer used
+  // row-parallel, so E (= rowptr[n], device-side) is never needed on the host
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_degree_init, dim3(rgnn_blocks(n, 256)), dim3(256), 0, s, rowptr, n, degree_out);
   hipLaunchKernelGGL(k_degree_edges, dim3(rgnn_blocks(n * 16, 256)), dim3(256), 0, s, rowptr, col, n, degree_out);
@@ -2126,10 +2107,12 @@ extern "C" int rgnn_invert_permutation(const int32_t* order, int64_t n, int32_t*
 
 extern "C" int rgnn_csr_by_target_symmetric(const int64_t* edge_index, const int32_t* rowptr_src, int64_t n,
                                             int64_t n_edges, const int32_t* target_rank, int32_t* rowptr_t,
-                                            int32_t* src_sorted, int32_t* perm, void* tmp, int32_t* status,
+                                            int32_t* src_sorted, int32_t* perm, int32_t* own_edge, void* tmp, int32_t* status,
                                             rgnn_stream_t stream) {
   RGNN_CHECK_ARG(n >= 0 && n_edges >= 0 && n_edges < ((int64_t)1 << 31), "bad sizes");
   RGNN_CHECK_ARG(rowptr_t && tmp && rowptr_src, "null pointers");
+  RGNN_CHECK_ARG(n_edges == 0 || (edge_index && src_sorted), "null edge arrays");
+  RGNN_CHECK_ARG(n_edges == 0 || (perm == nullptr) != (own_edge == nullptr), "exactly one of perm / own_edge");
   hipStream_t s = (hipStream_t)stream;
   int32_t* cnt = (int32_t*)tmp;
   void* scan_tmp = (char*)tmp + rgnn_align_up(4 * (n + 1), 256);
@@ -2137,29 +2120,9 @@ extern "C" int rgnn_csr_by_target_symmetric(const int64_t* edge_index, const int
   int rc = rgnn_exclusive_scan_i32(cnt, rowptr_t, n, scan_tmp, stream);
   if (rc) return rc;
   if (n_edges > 0) {
-    RGNN_CHECK_ARG(edge_index && src_sorted && perm, "null edge arrays");
+    // perm: the twin search, which checks the symmetry; own_edge: no search, the symmetry is the caller's claim (k_sym_csr)
     hipLaunchKernelGGL(k_sym_csr, dim3(rgnn_blocks(n_edges, 256)), dim3(256), 0, s, edge_index, n_edges, rowptr_src,
-                       target_rank, rowptr_t, perm, src_sorted, status);
-  }
-  RGNN_CHECK_LAUNCH();
-  return RGNN_OK;
-}
-
-extern "C" int rgnn_csr_by_target_symmetric_own(const int64_t* edge_index, const int32_t* rowptr_src, int64_t n, int64_t n_edges,
-                                                const int32_t* target_rank, int32_t* rowptr_t, int32_t* src_sorted,
-                                                int32_t* own_edge, void* tmp, int32_t* status, rgnn_stream_t stream) {
-  RGNN_CHECK_ARG(n >= 0 && n_edges >= 0 && n_edges < ((int64_t)1 << 31), "bad sizes");
-  RGNN_CHECK_ARG(rowptr_t && tmp && rowptr_src, "null pointers");
-  hipStream_t s = (hipStream_t)stream;
-  int32_t* cnt = (int32_t*)tmp;
-  void* scan_tmp = (char*)tmp + rgnn_align_up(4 * (n + 1), 256);
-  hipLaunchKernelGGL(k_sym_degree, dim3(rgnn_blocks(n + 1, 256)), dim3(256), 0, s, rowptr_src, target_rank, n, cnt);
-  int rc = rgnn_exclusive_scan_i32(cnt, rowptr_t, n, scan_tmp, stream);
-  if (rc) return rc;
-  if (n_edges > 0) {
-    RGNN_CHECK_ARG(edge_index && src_sorted && own_edge, "null edge arrays");
-    hipLaunchKernelGGL(k_sym_csr, dim3(rgnn_blocks(n_edges, 256)), dim3(256), 0, s, edge_index, n_edges, rowptr_src, target_rank,
-                       rowptr_t, (int32_t*)nullptr, src_sorted, status, own_edge);
+                       target_rank, rowptr_t, perm, src_sorted, status, own_edge);
   }
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
@@ -2183,22 +2146,12 @@ extern "C" int rgnn_csr_by_target_frames(const int64_t* edge_index, int64_t n, i
   return RGNN_OK;
 }
 
-static int csr_by_target_impl(const int64_t* edge_index, int64_t n, int64_t n_edges, const int32_t* target_rank,
-                              int32_t* rowptr_t, int32_t* src_sorted, int32_t* perm, void* tmp, rgnn_stream_t stream, bool ordered);
+// ordered == 0: without the stable ordering inside the segments (r06): the places the fill's atomics hand out ARE the result -- for
+// reductions that do not depend on the order of a segment's edges (max), whose callers save the ranking pass (59 us of a k = 20 batch
+// of 64 x 3000 points).
 extern "C" int rgnn_csr_by_target(const int64_t* edge_index, int64_t n, int64_t n_edges, const int32_t* target_rank,
-                                  int32_t* rowptr_t, int32_t* src_sorted, int32_t* perm, void* tmp,
+                                  int32_t* rowptr_t, int32_t* src_sorted, int32_t* perm, void* tmp, int32_t ordered,
                                   rgnn_stream_t stream) {
-  return csr_by_target_impl(edge_index, n, n_edges, target_rank, rowptr_t, src_sorted, perm, tmp, stream, true);
-}
-// ... without the stable ordering inside the segments (r06): the places the fill's atomics hand out ARE the result -- for reductions that
-// do not depend on the order of a segment's edges (max), whose callers save the ranking pass (59 us of a k = 20 batch of 64 x 3000 points).
-extern "C" int rgnn_csr_by_target_unordered(const int64_t* edge_index, int64_t n, int64_t n_edges, const int32_t* target_rank,
-                                            int32_t* rowptr_t, int32_t* src_sorted, int32_t* perm, void* tmp,
-                                            rgnn_stream_t stream) {
-  return csr_by_target_impl(edge_index, n, n_edges, target_rank, rowptr_t, src_sorted, perm, tmp, stream, false);
-}
-static int csr_by_target_impl(const int64_t* edge_index, int64_t n, int64_t n_edges, const int32_t* target_rank,
-                              int32_t* rowptr_t, int32_t* src_sorted, int32_t* perm, void* tmp, rgnn_stream_t stream, bool ordered) {
   RGNN_CHECK_ARG(n >= 0 && n_edges >= 0 && n_edges < ((int64_t)1 << 31), "bad sizes");
   RGNN_CHECK_ARG(rowptr_t && tmp, "null pointers");
   hipStream_t s = (hipStream_t)stream;

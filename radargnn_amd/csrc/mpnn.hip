@@ -743,20 +743,11 @@ int check_common(const float* Q, const float* We, const float* ea, int de, const
 
 }  // namespace
 
-extern "C" int rgnn_mpnn_aggregate_flags(const float* P, int64_t ldp, const float* p_bias, const float* Q, int64_t ldq,
-                                         const float* We, int64_t ldwe, const float* edge_attr_sorted, int32_t de,
-                                         const int32_t* rowptr_t, const int32_t* src_sorted, const int32_t* node_order,
-                                         const int32_t* chunk_start, int32_t n_chunks, int64_t n, int32_t d, int32_t aggr,
-                                         float* out, int64_t ldo, int32_t flags, rgnn_stream_t stream) {
-  return rgnn_mpnn_aggregate_absmax(P, ldp, p_bias, Q, ldq, We, ldwe, edge_attr_sorted, de, rowptr_t, src_sorted, node_order,
-                                    chunk_start, n_chunks, n, d, aggr, out, ldo, flags, nullptr, stream);
-}
-
-extern "C" int rgnn_mpnn_aggregate_absmax(const float* P, int64_t ldp, const float* p_bias, const float* Q, int64_t ldq,
-                                          const float* We, int64_t ldwe, const float* edge_attr_sorted, int32_t de,
-                                          const int32_t* rowptr_t, const int32_t* src_sorted, const int32_t* node_order,
-                                          const int32_t* chunk_start, int32_t n_chunks, int64_t n, int32_t d, int32_t aggr,
-                                          float* out, int64_t ldo, int32_t flags, float* out_absmax, rgnn_stream_t stream) {
+extern "C" int rgnn_mpnn_aggregate(const float* P, int64_t ldp, const float* p_bias, const float* Q, int64_t ldq,
+                                   const float* We, int64_t ldwe, const float* edge_attr_sorted, int32_t de,
+                                   const int32_t* rowptr_t, const int32_t* src_sorted, const int32_t* node_order,
+                                   const int32_t* chunk_start, int32_t n_chunks, int64_t n, int32_t d, int32_t aggr,
+                                   float* out, int64_t ldo, int32_t flags, float* out_absmax, rgnn_stream_t stream) {
   if (n == 0) return RGNN_OK;
   int rc = check_common(Q, We, edge_attr_sorted, de, rowptr_t, src_sorted, n, d, aggr);
   if (rc) return rc;
@@ -787,19 +778,7 @@ extern "C" int rgnn_mpnn_aggregate_max_arg(const float* p_bias, const float* Q, 
                                            const float* edge_attr_sorted, int32_t de, const int32_t* rowptr_t,
                                            const int32_t* src_sorted, const int32_t* node_order, const int32_t* chunk_start,
                                            int32_t n_chunks, int64_t n, int32_t d, float* out, int64_t ldo, uint16_t* arg_out,
-                                           int32_t flags, int32_t* arg_written, rgnn_stream_t stream) {
-  RGNN_CHECK_ARG(arg_written != nullptr, "null arg_written");
-  const int rc = rgnn_mpnn_aggregate_max_arg_absmax(p_bias, Q, ldq, We, ldwe, edge_attr_sorted, de, rowptr_t, src_sorted, node_order,
-                                                    chunk_start, n_chunks, n, d, out, ldo, arg_out, flags, arg_written, nullptr, stream);
-  *arg_written &= 1;
-  return rc;
-}
-
-extern "C" int rgnn_mpnn_aggregate_max_arg_absmax(const float* p_bias, const float* Q, int64_t ldq, const float* We, int64_t ldwe,
-                                                  const float* edge_attr_sorted, int32_t de, const int32_t* rowptr_t,
-                                                  const int32_t* src_sorted, const int32_t* node_order, const int32_t* chunk_start,
-                                                  int32_t n_chunks, int64_t n, int32_t d, float* out, int64_t ldo, uint16_t* arg_out,
-                                                  int32_t flags, int32_t* arg_written, float* out_absmax, rgnn_stream_t stream) {
+                                           int32_t flags, int32_t* arg_written, float* out_absmax, rgnn_stream_t stream) {
   RGNN_CHECK_ARG(arg_written != nullptr, "null arg_written");
   *arg_written = 0;
   if (n == 0) return RGNN_OK;
@@ -825,15 +804,6 @@ extern "C" int rgnn_mpnn_aggregate_max_arg_absmax(const float* p_bias, const flo
   }
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
-}
-
-extern "C" int rgnn_mpnn_aggregate(const float* P, int64_t ldp, const float* p_bias, const float* Q, int64_t ldq,
-                                   const float* We, int64_t ldwe, const float* edge_attr_sorted, int32_t de,
-                                   const int32_t* rowptr_t, const int32_t* src_sorted, const int32_t* node_order,
-                                   const int32_t* chunk_start, int32_t n_chunks, int64_t n, int32_t d, int32_t aggr,
-                                   float* out, int64_t ldo, rgnn_stream_t stream) {
-  return rgnn_mpnn_aggregate_flags(P, ldp, p_bias, Q, ldq, We, ldwe, edge_attr_sorted, de, rowptr_t, src_sorted, node_order,
-                                   chunk_start, n_chunks, n, d, aggr, out, ldo, 0, stream);
 }
 
 extern "C" int rgnn_mpnn_edge_hidden(const float* P, int64_t ldp, const float* p_bias, const float* Q, int64_t ldq,

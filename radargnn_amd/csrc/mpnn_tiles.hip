@@ -781,10 +781,12 @@ extern "C" int rgnn_mpnn_win_wplanes(const float* We, int64_t ldwe, int32_t de, 
   return RGNN_OK;
 }
 
-static int aggregate_win(const float* p_bias, const float* Q, int64_t ldq, const float* We, int64_t ldwe,
-                         const float* edge_attr_sorted, int32_t de, const int32_t* rowptr_t, const int32_t* src_sorted,
-                         const int32_t* node_order, int32_t* plan, int64_t n, int64_t n_edges, int32_t d, float* out,
-                         int64_t ldo, int32_t flags, float* out_absmax, const void* wplanes, rgnn_stream_t stream) {
+// wplanes: the operand image built ahead (rgnn_mpnn_win_wplanes from the SAME We / p_bias, which the per-target kernel still reads);
+// NULL: built into the plan's scratch in front of the launch
+extern "C" int rgnn_mpnn_aggregate_win(const float* p_bias, const float* Q, int64_t ldq, const float* We, int64_t ldwe,
+                                       const float* edge_attr_sorted, int32_t de, const int32_t* rowptr_t, const int32_t* src_sorted,
+                                       const int32_t* node_order, int32_t* plan, int64_t n, int64_t n_edges, int32_t d, float* out,
+                                       int64_t ldo, int32_t flags, float* out_absmax, const void* wplanes, rgnn_stream_t stream) {
   if (n == 0) return RGNN_OK;
   RGNN_CHECK_ARG(Q && rowptr_t && plan && out && d >= 1, "bad arguments");
   RGNN_CHECK_ARG((flags & ~RGNN_MPNN_SKIP_EMPTY_ROWS) == 0, "unknown flags");
@@ -833,23 +835,4 @@ static int aggregate_win(const float* p_bias, const float* Q, int64_t ldq, const
   }
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
-}
-
-extern "C" int rgnn_mpnn_aggregate_win(const float* p_bias, const float* Q, int64_t ldq, const float* We, int64_t ldwe,
-                                       const float* edge_attr_sorted, int32_t de, const int32_t* rowptr_t, const int32_t* src_sorted,
-                                       const int32_t* node_order, int32_t* plan, int64_t n, int64_t n_edges, int32_t d, float* out,
-                                       int64_t ldo, int32_t flags, float* out_absmax, rgnn_stream_t stream) {
-  return aggregate_win(p_bias, Q, ldq, We, ldwe, edge_attr_sorted, de, rowptr_t, src_sorted, node_order, plan, n, n_edges, d, out, ldo, flags,
-                       out_absmax, nullptr, stream);
-}
-
-// ... with the operand image built ahead (rgnn_mpnn_win_wplanes from the SAME We / p_bias, which the per-target kernel still reads)
-extern "C" int rgnn_mpnn_aggregate_win_planes(const float* p_bias, const float* Q, int64_t ldq, const float* We, int64_t ldwe,
-                                              const float* edge_attr_sorted, int32_t de, const int32_t* rowptr_t,
-                                              const int32_t* src_sorted, const int32_t* node_order, int32_t* plan, int64_t n,
-                                              int64_t n_edges, int32_t d, float* out, int64_t ldo, int32_t flags, float* out_absmax,
-                                              const void* wplanes, rgnn_stream_t stream) {
-  RGNN_CHECK_ARG(wplanes != nullptr, "null operand image");
-  return aggregate_win(p_bias, Q, ldq, We, ldwe, edge_attr_sorted, de, rowptr_t, src_sorted, node_order, plan, n, n_edges, d, out, ldo, flags,
-                       out_absmax, wplanes, stream);
 }

@@ -722,33 +722,11 @@ extern "C" int rgnn_bn_bwd_coef(const float* fwd_stats, int64_t panels_f, const 
   return RGNN_OK;
 }
 
-extern "C" int rgnn_batchnorm_finalize(const float* col_stats, int64_t panels, int64_t m, int32_t n, const float* gamma,
-                                       const float* beta, float* running_mean, float* running_var,
-                                       int64_t* num_batches_tracked, int32_t training, float momentum, float eps,
-                                       float* scale_shift, rgnn_stream_t stream) {
-  RGNN_CHECK_ARG(n >= 1 && scale_shift, "bad arguments");
-  RGNN_CHECK_ARG(!training || (col_stats && m >= 1 && panels >= 1), "training mode needs column statistics");
-  RGNN_CHECK_ARG(training || (running_mean && running_var), "eval mode needs running statistics");
-  return rgnn_batchnorm_finalize_bound(col_stats, panels, nullptr, nullptr, 0, nullptr, m, n, gamma, beta, running_mean, running_var,
-                                       num_batches_tracked, training, momentum, eps, scale_shift, nullptr, nullptr, stream);
-}
-
-extern "C" int rgnn_batchnorm_finalize_parts(const float* stats_a, int64_t panels_a, const int64_t* rows_a,
-                                             const float* stats_b, int64_t panels_b, const int64_t* rows_b, int64_t m,
-                                             int32_t n, const float* gamma, const float* beta, float* running_mean,
-                                             float* running_var, int64_t* num_batches_tracked, int32_t training,
-                                             float momentum, float eps, float* scale_shift, rgnn_stream_t stream) {
-  return rgnn_batchnorm_finalize_bound(stats_a, panels_a, rows_a, stats_b, panels_b, rows_b, m, n, gamma, beta, running_mean,
-                                       running_var, num_batches_tracked, training, momentum, eps, scale_shift, nullptr, nullptr,
-                                       stream);
-}
-
-extern "C" int rgnn_batchnorm_finalize_bound(const float* stats_a, int64_t panels_a, const int64_t* rows_a,
-                                             const float* stats_b, int64_t panels_b, const int64_t* rows_b, int64_t m,
-                                             int32_t n, const float* gamma, const float* beta, float* running_mean,
-                                             float* running_var, int64_t* num_batches_tracked, int32_t training,
-                                             float momentum, float eps, float* scale_shift, const float* in_bound,
-                                             float* out_bound, rgnn_stream_t stream) {
+extern "C" int rgnn_batchnorm_finalize(const float* stats_a, int64_t panels_a, const int64_t* rows_a, const float* stats_b,
+                                       int64_t panels_b, const int64_t* rows_b, int64_t m, int32_t n, const float* gamma,
+                                       const float* beta, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                       int32_t training, float momentum, float eps, float* scale_shift, const float* in_bound,
+                                       float* out_bound, rgnn_stream_t stream) {
   RGNN_CHECK_ARG(n >= 1 && scale_shift, "bad arguments");
   RGNN_CHECK_ARG(out_bound == nullptr || in_bound != nullptr, "out_bound needs in_bound");
   RGNN_CHECK_ARG(!training || (stats_a && m >= 1 && panels_a >= 1 && (stats_b == nullptr || panels_b >= 1)),

@@ -471,15 +471,8 @@ extern "C" int32_t rgnn_wgrad_slabs(int64_t m, int32_t n, int32_t k1, int32_t k2
 
 extern "C" int rgnn_wgrad(const float* G, int64_t ldg, int32_t n, const float* A1, int64_t lda1, int32_t k1, const float* A2,
                           int64_t lda2, int32_t k2, int32_t with_ones, int64_t m, const int32_t* row_index, const int64_t* m_dev,
-                          float* partial, float* dW, rgnn_stream_t stream) {
-  return rgnn_wgrad_bounds(G, ldg, n, A1, lda1, k1, A2, lda2, k2, with_ones, m, row_index, m_dev, nullptr, nullptr, nullptr, partial, dW,
-                           stream);
-}
-
-extern "C" int rgnn_wgrad_bounds(const float* G, int64_t ldg, int32_t n, const float* A1, int64_t lda1, int32_t k1, const float* A2,
-                                 int64_t lda2, int32_t k2, int32_t with_ones, int64_t m, const int32_t* row_index, const int64_t* m_dev,
-                                 const float* g_bound, const float* a1_bound, const float* a2_bound, float* partial, float* dW,
-                                 rgnn_stream_t stream) {
+                          const float* g_bound, const float* a1_bound, const float* a2_bound, float* partial, float* dW,
+                          rgnn_stream_t stream) {
   RGNN_CHECK_ARG(m >= 0 && n >= 0 && k1 >= 0 && k2 >= 0, "negative sizes");
   const int Kt = k1 + k2 + (with_ones ? 1 : 0);
   if (n == 0 || Kt == 0) return RGNN_OK;

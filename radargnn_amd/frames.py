@@ -291,7 +291,7 @@ class HotPath:
     microseconds each; C1: 0.56 ms eager, 0.37 ms replayed).  A batch runs eagerly the first time it is seen and is captured
     on its next occurrence; one captured graph is kept at a time.  Results are identical either way (same kernels, same
     order).  kNN graphs have E = N k; for radius graphs the capture is sized for the edge count the eager pass found, and
-    the fill pass verifies it on the device (rgnn_radius_graph_fill_checked): if the batch's points were modified in place
+    the fill pass verifies it on the device (rgnn_radius_graph_fill with a status word): if the batch's points were modified in place
     so that the count changed, the replay leaves the previous outputs and sets STATUS_EDGE_COUNT_CHANGED
     (``GraphBatch.check()`` raises).
 

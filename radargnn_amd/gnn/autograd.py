@@ -221,8 +221,8 @@ class ConvFoldedFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dh, _dstats):
-        # the dgrad launches take the f16x2 form when their operands carry bounds: dh from rgnn_bn_bwd_apply_absmax, dM from the
-        # launch that wrote it, dQ from rgnn_mpnn_max_bwd_absmax -- tracked in the pool of the forward pass
+        # the dgrad launches take the f16x2 form when their operands carry bounds: dh from rgnn_bn_bwd_apply, dM from the
+        # launch that wrote it, dQ from rgnn_mpnn_max_bwd -- tracked in the pool of the forward pass
         with ops.using_bounds(ctx.pool):
             return ConvFoldedFn._backward(ctx, dh)
 

@@ -272,9 +272,8 @@ class GridHash:
 
     def build(self, cell_size: float = 0.0, pts_per_cell: float = 2.0, max_frame_points: int = 0) -> "GridHash":
         """``max_frame_points`` > 0: the caller knows (host copy of the frame sizes) that no frame is larger -- moderately sized
-        frames are then binned by one launch instead of five (rgnn_grid_build_frames)."""
-        check(lib.rgnn_grid_build_frames(C.byref(self.desc), float(cell_size), float(pts_per_cell), int(max_frame_points),
-                                         _stream()))
+        frames are then binned by one launch instead of five."""
+        check(lib.rgnn_grid_build(C.byref(self.desc), float(cell_size), float(pts_per_cell), int(max_frame_points), _stream()))
         return self
 
     def _order_views(self):
@@ -342,7 +341,7 @@ def radius_graph_fill(g: "GridHash", rowptr: torch.Tensor, r: float, n_edges: in
                       guard_status: Optional[torch.Tensor] = None, relative_position: Optional[str] = None):
     """Pass 2: -> col int32 [E] (ascending per row), edge_index int64 [2,E].
     ``guard_status``: n_edges was not just read back from rowptr (captured step): the kernels verify rowptr[n] == n_edges on
-    the device, write nothing otherwise and set STATUS_EDGE_COUNT_CHANGED in it (rgnn_radius_graph_fill_checked).
+    the device, write nothing otherwise and set STATUS_EDGE_COUNT_CHANGED in it.
     ``relative_position`` ("directed" | "undirected"): also return the relative_position edge attributes float32 [E, 2] as a
     third value -- written by the same launch (rgnn_radius_graph_rows)."""
     col = torch.empty(n_edges, dtype=torch.int32, device=rowptr.device)
@@ -354,12 +353,8 @@ def radius_graph_fill(g: "GridHash", rowptr: torch.Tensor, r: float, n_edges: in
                                          _ptr(guard_status), _ptr(rel), 1 if relative_position == "undirected" else 0, _stream()))
         return (col, ei, rel) if relative_position else (col, ei)
     tmp = torch.empty(max(2 * n_edges, 1), dtype=torch.int32, device=rowptr.device)
-    if guard_status is not None:
-        check(lib.rgnn_radius_graph_fill_checked(C.byref(g.desc), float(r), _ptr(rowptr), _ptr(col), _ptr(ei), n_edges,
-                                                 _ptr(tmp), _ptr(guard_status), _stream()))
-    else:
-        check(lib.rgnn_radius_graph_fill(C.byref(g.desc), float(r), _ptr(rowptr), _ptr(col), _ptr(ei), n_edges, _ptr(tmp),
-                                         _stream()))
+    check(lib.rgnn_radius_graph_fill(C.byref(g.desc), float(r), _ptr(rowptr), _ptr(col), _ptr(ei), n_edges, _ptr(tmp),
+                                     _ptr(guard_status), _stream()))
     if relative_position:
         rel, _ = edge_features(g.X, g.X, ei, ["relative_position"], relative_position, dtype=torch.float32)   # (V is not read)
         return col, ei, rel
@@ -408,25 +403,21 @@ def knn_graph(X: torch.Tensor, frame_ptr: torch.Tensor, k: int, status: Optional
     n = g.n
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=X.device)
-    if (relative_position or degree_init) and k <= 64:
-        # the write-out of the search also emits the relative_position attributes ("directed" | "undirected") and presets the
-        # undirected-degree array with the out-degrees (rgnn_knn_graph_attrs): returned as 4th / 5th value
-        rel = torch.empty((g.n * k, 2), dtype=torch.float32, device=X.device) if relative_position else None
-        deg = torch.empty(g.n, dtype=torch.int32, device=X.device) if degree_init else None
-        # (with the largest frame known: small frames are searched by brute force per frame, rgnn_knn_graph_frames)
-        check(lib.rgnn_knn_graph_frames(C.byref(g.desc), int(k), int(max_frame_points), _ptr(nbr), _ptr(ei), _ptr(status), _ptr(rel),
-                                        1 if relative_position == "undirected" else 0, _ptr(deg), _stream()))
-        return nbr, ei, status, rel, deg
-    check(lib.rgnn_knn_graph_frames(C.byref(g.desc), int(k), int(max_frame_points), _ptr(nbr), _ptr(ei), _ptr(status), None, 0, None,
-                                    _stream()))
-    return (nbr, ei, status, None, None) if (relative_position or degree_init) else (nbr, ei, status)
+    # k <= 64: the write-out of the search also emits the relative_position attributes ("directed" | "undirected") and presets the
+    # undirected-degree array with the out-degrees: returned as 4th / 5th value (None beyond that k)
+    rel = torch.empty((g.n * k, 2), dtype=torch.float32, device=X.device) if relative_position and k <= 64 else None
+    deg = torch.empty(g.n, dtype=torch.int32, device=X.device) if degree_init and k <= 64 else None
+    # (with the largest frame known: small frames are searched by brute force per frame)
+    check(lib.rgnn_knn_graph(C.byref(g.desc), int(k), int(max_frame_points), _ptr(nbr), _ptr(ei), _ptr(status), _ptr(rel),
+                             1 if rel is not None and relative_position == "undirected" else 0, _ptr(deg), _stream()))
+    return (nbr, ei, status, rel, deg) if (relative_position or degree_init) else (nbr, ei, status)
 
 
 def undirected_degree(rowptr: torch.Tensor, col: torch.Tensor, n: int) -> torch.Tensor:
     _dev(rowptr, "rowptr", torch.int32)
     _dev(col, "col", torch.int32)
     deg = torch.empty(n, dtype=torch.int32, device=rowptr.device)
-    check(lib.rgnn_undirected_degree(_ptr(rowptr), _ptr(col.contiguous()), n, None, _ptr(deg), _stream()))
+    check(lib.rgnn_undirected_degree(_ptr(rowptr), _ptr(col.contiguous()), n, _ptr(deg), _stream()))
     return deg
 
 
@@ -489,18 +480,15 @@ def csr_by_target(edge_index: torch.Tensor, n: int, target_rank: Optional[torch.
         _dev(symmetric_rows, "symmetric_rows", torch.int32)
         if symmetric_rows.numel() != n + 1:
             raise ValueError("symmetric_rows must be [n + 1]")
-        if own_edges:
-            # (no twin search: the third result is the OWN out-edge at the slot of every in-edge -- rgnn_csr_by_target_symmetric_own)
-            check(lib.rgnn_csr_by_target_symmetric_own(_ptr(ei), _ptr(symmetric_rows), n, e, _ptr(target_rank), _ptr(rowptr_t),
-                                                       _ptr(src), _ptr(perm), _ptr(tmp), _ptr(status), _stream()))
-            return rowptr_t, src, perm
-        check(lib.rgnn_csr_by_target_symmetric(_ptr(ei), _ptr(symmetric_rows), n, e, _ptr(target_rank), _ptr(rowptr_t),
-                                               _ptr(src), _ptr(perm), _ptr(tmp), _ptr(status), _stream()))
+        # ``own_edges``: no twin search -- the third result is the OWN out-edge at the slot of every in-edge (the own_edge argument)
+        check(lib.rgnn_csr_by_target_symmetric(_ptr(ei), _ptr(symmetric_rows), n, e, _ptr(target_rank), _ptr(rowptr_t), _ptr(src),
+                                               None if own_edges else _ptr(perm), _ptr(perm) if own_edges else None, _ptr(tmp),
+                                               _ptr(status), _stream()))
         return rowptr_t, src, perm
-    # ``ordered=False``: the order of a target's in-edges is whatever the fill's atomics made it (rgnn_csr_by_target_unordered) -- for
-    # callers whose reduction does not depend on it (max aggregation): one pass over the edges less
-    fn = lib.rgnn_csr_by_target if ordered else lib.rgnn_csr_by_target_unordered
-    check(fn(_ptr(ei), n, e, _ptr(target_rank), _ptr(rowptr_t), _ptr(src), _ptr(perm), _ptr(tmp), _stream()))
+    # ``ordered=False``: the order of a target's in-edges is whatever the fill's atomics made it -- for callers whose reduction does
+    # not depend on it (max aggregation): one pass over the edges less
+    check(lib.rgnn_csr_by_target(_ptr(ei), n, e, _ptr(target_rank), _ptr(rowptr_t), _ptr(src), _ptr(perm), _ptr(tmp),
+                                 1 if ordered else 0, _stream()))
     return rowptr_t, src, perm
 
 
@@ -1230,7 +1218,7 @@ def apply_table_reference(x: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
 class StatParts:
     """Column statistics of one layer output left by up to two row-subset launches, each in a buffer of its own:
     ``parts`` = [(stats [panels, STAT_ROWS, C], row count int64 [1] on the device or None), ...].  Only the panels a launch really
-    wrote are summed (rgnn_batchnorm_finalize_parts), so the buffers are allocated uninitialised."""
+    wrote are summed (rgnn_batchnorm_finalize rows_a / rows_b), so the buffers are allocated uninitialised."""
     __slots__ = ("parts",)
 
     def __init__(self, parts):
@@ -1251,29 +1239,16 @@ def batchnorm_finalize(stats, m: int, n: int, gamma, beta, running_mean, running
     dev = (stats if stats is not None else running_mean).device
     ss = torch.empty((AFFINE_ROWS, n), dtype=torch.float32, device=dev)
     out_bound = ctx().bounds.word() if (ctx().bounds is not None and in_bound is not None) else None
-    if out_bound is not None:
-        if isinstance(stats, StatParts):
-            (sa, ra), (sb, rb) = stats.parts[0], (stats.parts[1] if len(stats.parts) > 1 else (None, None))
-        else:
-            sa, ra, sb, rb = stats, None, None, None
-        check(lib.rgnn_batchnorm_finalize_bound(_ptr(sa), 0 if sa is None else sa.shape[0], _ptr(ra), _ptr(sb),
-                                                0 if sb is None else sb.shape[0], _ptr(rb), m, n, _ptr(gamma), _ptr(beta),
-                                                _ptr(running_mean), _ptr(running_var), _ptr(num_batches_tracked),
-                                                1 if training else 0, float(momentum), float(eps), _ptr(ss), _ptr(in_bound),
-                                                _ptr(out_bound), _stream()))
-        set_bound(ss, out_bound)
-        return ss
     if isinstance(stats, StatParts):
         (sa, ra), (sb, rb) = stats.parts[0], (stats.parts[1] if len(stats.parts) > 1 else (None, None))
-        check(lib.rgnn_batchnorm_finalize_parts(_ptr(sa), sa.shape[0], _ptr(ra), _ptr(sb), 0 if sb is None else sb.shape[0],
-                                                _ptr(rb), m, n, _ptr(gamma), _ptr(beta), _ptr(running_mean),
-                                                _ptr(running_var), _ptr(num_batches_tracked), 1 if training else 0,
-                                                float(momentum), float(eps), _ptr(ss), _stream()))
-        return ss
-    panels = 0 if stats is None else stats.shape[0]
-    check(lib.rgnn_batchnorm_finalize(_ptr(stats), panels, m, n, _ptr(gamma), _ptr(beta), _ptr(running_mean),
-                                      _ptr(running_var), _ptr(num_batches_tracked), 1 if training else 0,
-                                      float(momentum), float(eps), _ptr(ss), _stream()))
+    else:
+        sa, ra, sb, rb = stats, None, None, None
+    check(lib.rgnn_batchnorm_finalize(_ptr(sa), 0 if sa is None else sa.shape[0], _ptr(ra), _ptr(sb), 0 if sb is None else sb.shape[0],
+                                      _ptr(rb), m, n, _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var),
+                                      _ptr(num_batches_tracked), 1 if training else 0, float(momentum), float(eps), _ptr(ss),
+                                      None if out_bound is None else _ptr(in_bound), _ptr(out_bound), _stream()))
+    if out_bound is not None:
+        set_bound(ss, out_bound)
     return ss
 
 
@@ -1450,10 +1425,10 @@ def mpnn_aggregate(P, p_bias, Q, We, ea_sorted, rowptr_t, src_sorted, aggr: str,
     out = padded_rows(n, d, Q.device)                        # rows start on 128-byte lines (see padded_rows)
     word = ctx().bounds.word() if ctx().bounds is not None else None     # max |out|: the update GEMM's A2 bound (f16x2 form)
     tok = ctx().profiler.begin("mpnn_aggregate") if ctx().profiler is not None else None
-    check(lib.rgnn_mpnn_aggregate_absmax(_ptr(P), 0 if P is None else _ld(P), _ptr(p_bias), _ptr(Q), _ld(Q), _ptr(We),
-                                         0 if We is None else _ld(We), _ptr(ea_sorted), de, _ptr(rowptr_t), _ptr(src_sorted if src_sorted.numel() else rowptr_t),
-                                         _ptr(node_order), _ptr(chunks), 0 if chunks is None else chunks.numel() - 1025, n, d,
-                                         AGGR_CODES[aggr], _ptr(out), _ld(out), 1 if skip_empty_rows else 0, _ptr(word), _stream()))
+    check(lib.rgnn_mpnn_aggregate(_ptr(P), 0 if P is None else _ld(P), _ptr(p_bias), _ptr(Q), _ld(Q), _ptr(We),
+                                  0 if We is None else _ld(We), _ptr(ea_sorted), de, _ptr(rowptr_t), _ptr(src_sorted if src_sorted.numel() else rowptr_t),
+                                  _ptr(node_order), _ptr(chunks), 0 if chunks is None else chunks.numel() - 1025, n, d,
+                                  AGGR_CODES[aggr], _ptr(out), _ld(out), 1 if skip_empty_rows else 0, _ptr(word), _stream()))
     if tok is not None:
         ctx().profiler.end(tok, n=n, d=d, de=de, e=src_sorted.numel())
     set_bound(out, word)
@@ -1509,13 +1484,10 @@ def mpnn_aggregate_win(p_bias, Q, We, ea_sorted, rowptr_t, src_sorted, plan: tor
     word = ctx().bounds.word() if ctx().bounds is not None else None
     tok = ctx().profiler.begin("mpnn_aggregate") if ctx().profiler is not None else None
     planes = _win_operand_image(We, p_bias, d, de)
-    common = (_ptr(p_bias), _ptr(Q), _ld(Q), _ptr(We), 0 if We is None else _ld(We), _ptr(ea_sorted), de,
-              _ptr(rowptr_t), _ptr(src_sorted if src_sorted.numel() else rowptr_t), _ptr(node_order), _ptr(plan), n,
-              src_sorted.numel(), d, _ptr(out), _ld(out), 1 if skip_empty_rows else 0, _ptr(word))
-    if planes is not None:
-        check(lib.rgnn_mpnn_aggregate_win_planes(*common, _ptr(planes), _stream()))
-    else:
-        check(lib.rgnn_mpnn_aggregate_win(*common, _stream()))
+    check(lib.rgnn_mpnn_aggregate_win(_ptr(p_bias), _ptr(Q), _ld(Q), _ptr(We), 0 if We is None else _ld(We), _ptr(ea_sorted), de,
+                                      _ptr(rowptr_t), _ptr(src_sorted if src_sorted.numel() else rowptr_t), _ptr(node_order), _ptr(plan), n,
+                                      src_sorted.numel(), d, _ptr(out), _ld(out), 1 if skip_empty_rows else 0, _ptr(word), _ptr(planes),
+                                      _stream()))
     if tok is not None:
         ctx().profiler.end(tok, n=n, d=d, de=de, e=src_sorted.numel(), win=True)
     COUNTERS["mpnn_win"] = COUNTERS.get("mpnn_win", 0) + 1
@@ -1535,10 +1507,10 @@ def mpnn_aggregate_max_arg(p_bias, Q, We, ea_sorted, rowptr_t, src_sorted, node_
     written = C.c_int32(0)
     word = ctx().bounds.word() if ctx().bounds is not None else None     # max |out|: the update GEMM's A2 bound (f16x2 form)
     tok = ctx().profiler.begin("mpnn_aggregate") if ctx().profiler is not None else None
-    check(lib.rgnn_mpnn_aggregate_max_arg_absmax(_ptr(p_bias), _ptr(Q), _ld(Q), _ptr(We), 0 if We is None else _ld(We), _ptr(ea_sorted),
-                                                 de, _ptr(rowptr_t), _ptr(src_sorted if src_sorted.numel() else rowptr_t), _ptr(node_order),
-                                                 _ptr(chunks), 0 if chunks is None else chunks.numel() - 1025, n, d, _ptr(out), d, _ptr(arg),
-                                                 1 if skip_empty_rows else 0, C.byref(written), _ptr(word), _stream()))
+    check(lib.rgnn_mpnn_aggregate_max_arg(_ptr(p_bias), _ptr(Q), _ld(Q), _ptr(We), 0 if We is None else _ld(We), _ptr(ea_sorted),
+                                          de, _ptr(rowptr_t), _ptr(src_sorted if src_sorted.numel() else rowptr_t), _ptr(node_order),
+                                          _ptr(chunks), 0 if chunks is None else chunks.numel() - 1025, n, d, _ptr(out), d, _ptr(arg),
+                                          1 if skip_empty_rows else 0, C.byref(written), _ptr(word), _stream()))
     if tok is not None:
         ctx().profiler.end(tok, n=n, d=d, de=de, e=src_sorted.numel())
     set_bound(out, word if (written.value & 2) else None)
@@ -1593,8 +1565,8 @@ def bn_bwd_stats(dy: torch.Tensor, y: Optional[torch.Tensor], h: torch.Tensor, t
         table = _dev(table, "table", torch.float32).contiguous()
     m, n = h.shape
     part = torch.empty((max(stat_panels(m), 1), 2, n), dtype=torch.float32, device=h.device)
-    check(lib.rgnn_bn_bwd_stats_table(_ptr(dy), _ld(dy), _ptr(y), 0 if y is None else _ld(y), _ptr(table), _ptr(h), _ld(h), m, n,
-                                      _ptr(part), _stream()))
+    check(lib.rgnn_bn_bwd_stats(_ptr(dy), _ld(dy), _ptr(y), 0 if y is None else _ld(y), _ptr(table), _ptr(h), _ld(h), m, n,
+                                _ptr(part), _stream()))
     return part
 
 
@@ -1624,8 +1596,8 @@ def bn_bwd_apply(dy: torch.Tensor, y: Optional[torch.Tensor], h: torch.Tensor, c
     coef = _dev(coef, "coef", torch.float32).contiguous()
     dx = torch.empty((m, n), dtype=torch.float32, device=h.device)
     word = ctx().bounds.word() if ctx().bounds is not None else None     # max |dx|: the dgrad launches that read it (f16x2 form)
-    check(lib.rgnn_bn_bwd_apply_table(_ptr(dy), _ld(dy), _ptr(y), 0 if y is None else _ld(y), _ptr(table), _ptr(h), _ld(h), _ptr(coef),
-                                      m, n, _ptr(dx), n, _ptr(word), _stream()))
+    check(lib.rgnn_bn_bwd_apply(_ptr(dy), _ld(dy), _ptr(y), 0 if y is None else _ld(y), _ptr(table), _ptr(h), _ld(h), _ptr(coef),
+                                m, n, _ptr(dx), n, _ptr(word), _stream()))
     set_bound(dx, word)
     return dx
 
@@ -1670,10 +1642,10 @@ def mpnn_aggregate_bwd(dM, Q, We, ea_sorted, rowptr_t, src_sorted, aggr: str, so
         else:
             arg = torch.empty((n, d), dtype=torch.int16, device=dev)
         word = ctx().bounds.word() if ctx().bounds is not None else None  # max |dQ|: the dx launch reads [dh | dQ] (f16x2 form)
-        check(lib.rgnn_mpnn_max_bwd_absmax(_ptr(dM), _ld(dM), _ptr(Q), _ld(Q), _ptr(We), _ld(We), _ptr(ea_sorted), de, _ptr(rowptr_t),
-                                           _ptr(src_sorted), _ptr(tgt_sorted), _ptr(eloc_sorted), _ptr(node_order), n, d, _ptr(rowptr_s),
-                                           _ptr(tnode), _ptr(tloc), n_edges, _ptr(arg), 1 if have_arg else 0, _ptr(part), _ptr(dQ), d,
-                                           _ptr(dea), _ptr(dWe), _ptr(word), _stream()))
+        check(lib.rgnn_mpnn_max_bwd(_ptr(dM), _ld(dM), _ptr(Q), _ld(Q), _ptr(We), _ld(We), _ptr(ea_sorted), de, _ptr(rowptr_t),
+                                    _ptr(src_sorted), _ptr(tgt_sorted), _ptr(eloc_sorted), _ptr(node_order), n, d, _ptr(rowptr_s),
+                                    _ptr(tnode), _ptr(tloc), n_edges, _ptr(arg), 1 if have_arg else 0, _ptr(part), _ptr(dQ), d,
+                                    _ptr(dea), _ptr(dWe), _ptr(word), _stream()))
         set_bound(dQ, word)
         return dQ, dea, dWe
     dea = torch.empty((n_edges, de), dtype=torch.float32, device=dev) if de else None
@@ -1742,9 +1714,9 @@ def linear_wgrad(g: torch.Tensor, a1: torch.Tensor, a2: Optional[torch.Tensor] =
                 if rows.numel() and float(rows.abs().max()) > float(b_.max()) * (1 + 1e-6):
                     raise RuntimeError(f"ops.linear_wgrad: operand {nm} exceeds the bound attached to it "
                                        f"({float(rows.abs().max())} > {float(b_.max())})")
-    check(lib.rgnn_wgrad_bounds(_ptr(g), _ld(g), n, _ptr(a1), _ld(a1), k1, _ptr(a2), 0 if a2 is None else _ld(a2), k2,
-                                1 if with_bias else 0, m, _ptr(row_index), _ptr(m_dev), _ptr(bg) if f16 else None,
-                                _ptr(b1) if f16 else None, _ptr(b2) if f16 else None, _ptr(part), _ptr(dw), _stream()))
+    check(lib.rgnn_wgrad(_ptr(g), _ld(g), n, _ptr(a1), _ld(a1), k1, _ptr(a2), 0 if a2 is None else _ld(a2), k2,
+                         1 if with_bias else 0, m, _ptr(row_index), _ptr(m_dev), _ptr(bg) if f16 else None,
+                         _ptr(b1) if f16 else None, _ptr(b2) if f16 else None, _ptr(part), _ptr(dw), _stream()))
     COUNTERS["wgrad_f16x2" if f16 else "wgrad_other"] = COUNTERS.get("wgrad_f16x2" if f16 else "wgrad_other", 0) + 1
     return dw
 

@@ -129,7 +129,7 @@ def test_det_net_backward_matches_float64_autograd(rg, case):
 
 def test_training_in_the_f16x2_form_with_every_bound_verified(rg, monkeypatch):
     """ops.TRAIN_F16X2: a recorded forward tracks bounds like the inference one and its backward goes on in the same pool -- max |M|
-    from rgnn_mpnn_aggregate_max_arg_absmax, max |dh| from rgnn_bn_bwd_apply_absmax, max |dQ| from rgnn_mpnn_max_bwd_absmax, the
+    from rgnn_mpnn_aggregate_max_arg, max |dh| from rgnn_bn_bwd_apply, max |dQ| from rgnn_mpnn_max_bwd, the
     dense launches' own outputs -- so forward AND dgrad launches take the f16x2 form.  Widths above the 32-column floor of the
     split-operand kernels; RGNN_CHECK_BOUNDS compares every bound a launch consumes with the operand it describes (also on
     autograd's thread); gradients against float64 autograd at the tolerance of the bf16x3 path."""
@@ -300,7 +300,7 @@ def test_batchnorm_backward_mask_from_the_apply_table_gives_the_bits_of_the_mask
                                                  (4097, 128, 272, 544, 3e3, 1e-3, 1e-3), (3000, 64, 272, 68, 1e-6, 1e4, 2e2),
                                                  (9000, 5, 0, 48, 1.0, 1e-5, 1.0), (1500, 96, 40, 100, 1e12, 1e-12, 1e-9)])
 def test_weight_gradient_in_the_f16x2_form_matches_float64(rg, m, k1, k2, n, sg, s1, s2):
-    """rgnn_wgrad_bounds: both operands pre-scaled by powers of two from their bounds, two f16 terms, three products -- against float64
+    """rgnn_wgrad with bounds: both operands pre-scaled by powers of two from their bounds, two f16 terms, three products -- against float64
     on operands of very different magnitudes (the column of ones travels as 2^14 after the pre-scale whatever the scale of A is),
     blocks of A a few decades apart, over all rows and over a row list; the error is measured against bound(G) bound(A) like the
     forward f16x2 form's (tests/test_gpu_f16x2.py), and next to the bf16x3 form on the same data."""
@@ -521,7 +521,7 @@ def test_backward_entry_points_on_empty_inputs(rg):
     dW = torch.full((6, 9), 7.0, device="cuda")
     part = torch.empty(16, device="cuda")
     g = torch.empty((0, 6), device="cuda"); a = torch.empty((0, 8), device="cuda")
-    rc = lib.rgnn_wgrad(None, 6, 6, None, 8, 8, None, 0, 0, 1, 0, None, None, part.data_ptr(), dW.data_ptr(), None)
+    rc = lib.rgnn_wgrad(None, 6, 6, None, 8, 8, None, 0, 0, 1, 0, None, None, None, None, None, part.data_ptr(), dW.data_ptr(), None)
     assert rc == 0 and float(dW.abs().max()) == 0.0
     n, d, de = 5, 8, 2
     dQ = torch.full((n, d), 3.0, device="cuda"); dWe = torch.full((d, de), 3.0, device="cuda")

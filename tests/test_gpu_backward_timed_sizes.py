@@ -302,7 +302,7 @@ def test_weight_gradient_at_the_step_sizes(rg, m, k1, k2, n):
 @pytest.mark.parametrize("c", [224, 128, 64])
 @pytest.mark.parametrize("relu,from_table", [(True, True), (True, False), (False, False)])
 def test_batchnorm_backward_chain_at_192000_rows(rg, monkeypatch, c, relu, from_table):
-    """AG.batch_norm_act's backward (rgnn_bn_bwd_stats_table -> rgnn_bn_bwd_coef -> rgnn_bn_bwd_apply_table) against the float64
+    """AG.batch_norm_act's backward (rgnn_bn_bwd_stats -> rgnn_bn_bwd_coef -> rgnn_bn_bwd_apply) against the float64
     formula dh = gamma rstd (g - mean g - xhat mean(g xhat)), g = relu'(y) dy with the mask taken from the DEVICE's y (torch's ReLU
     backward), dgamma = sum g xhat, dbeta = sum g."""
     fr, gnn, ops, _ = rg

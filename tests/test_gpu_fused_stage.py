@@ -27,7 +27,7 @@ def _dense_cluster_frame(n, seed, spread):
 
 @pytest.mark.parametrize("r,frames", [(1.0, "radar"), (2.5, "mixed"), (1.0, "dense")])
 def test_one_launch_radius_stage_equals_the_split_launches(r, frames):
-    """rgnn_grid_build_frames (hint) + rgnn_radius_graph_rows against rgnn_grid_build + rgnn_radius_graph_fill +
+    """rgnn_grid_build with the hint + rgnn_radius_graph_rows against rgnn_grid_build without + rgnn_radius_graph_fill +
     rgnn_edge_features: rowptr, col, edge_index and the float32 relative_position attributes bit-equal -- rows from the count
     pass's cache, dense rows ranked from LDS (49 ... 512 neighbours) and from the scratch (> 512)."""
     from radargnn_amd import ops
@@ -112,7 +112,7 @@ def test_tiny_mlp2_equals_gather_and_two_linear_layers():
 
 
 def test_own_edge_map_of_a_symmetric_graph_replaces_the_twin_search_for_antisymmetric_attributes(monkeypatch):
-    """rgnn_csr_by_target_symmetric_own: same rows and sources as the build that searches every edge's twin, and for
+    """rgnn_csr_by_target_symmetric with own_edge: same rows and sources as the build that searches every edge's twin, and for
     relative_position in directed mode the attributes in target order are EXACTLY minus those of the own edge at the slot -- so the
     HotPath's logits are the same bits with and without the search."""
     from radargnn_amd import frames as fr, ops

@@ -569,7 +569,7 @@ def test_linear_applies_the_previous_batchnorm_inside_its_a_operand(rg, monkeypa
 
 
 def test_batchnorm_finalize_over_two_row_subset_launches_reads_live_panels_only(rg):
-    """rgnn_batchnorm_finalize_parts: the statistics of one layer output come from two row-subset launches with a buffer each;
+    """rgnn_batchnorm_finalize with two parts: the statistics of one layer output come from two row-subset launches with a buffer each;
     only the ceil(rows / 128) panels a launch wrote are read (everything else is poisoned with NaN here), and the result equals
     the one-buffer finalize over zero-filled buffers (up to the order the panels are added in)."""
     _, ops = rg

@@ -530,7 +530,7 @@ def test_side_streams_run_beside_each_other_and_the_default_stream():
 @pytest.mark.gpu
 def test_unordered_csr_gives_the_same_bits_for_max_aggregation(monkeypatch):
     """r06: with max aggregation HotPath builds the CSR by target of a kNN batch without the stable order inside the segments
-    (rgnn_csr_by_target_unordered: a maximum does not depend on the order of a target's in-edges).  Same logits and boxes, bit for bit,
+    (rgnn_csr_by_target with ordered = 0: a maximum does not depend on the order of a target's in-edges).  Same logits and boxes, bit for bit,
     as with the ordered build; mean / add models keep the ordered build."""
     from radargnn_amd import frames as fr, gnn
     frames = [synthetic.radarscenes_frame(i) for i in range(4)]

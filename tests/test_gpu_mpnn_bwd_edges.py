@@ -1,4 +1,4 @@
-"""The backward of the fused aggregation (csrc/backward.hip: rgnn_mpnn_aggregate_bwd, rgnn_mpnn_max_bwd[_absmax],
+"""The backward of the fused aggregation (csrc/backward.hip: rgnn_mpnn_aggregate_bwd, rgnn_mpnn_max_bwd,
 rgnn_segment_reduce_bwd) and the forward that records the winners (k_mpnn_max<ARG>, csrc/mpnn.hip) ON their internal thresholds:
 hand-built graphs with in-degrees around the 128-edge passes, the 8-edge one-element-per-lane pass, the 32-edge buffer and the
 60-edge blocks, out-degrees around the blocks of 64 and trips of 4 of the node half, 1 .. 5 nodes (slots without a segment), slot

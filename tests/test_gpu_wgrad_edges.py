@@ -56,7 +56,7 @@ def wgrad(ops, d, ones, bounds=None):
 
 
 def raw_wgrad(ops, d, ones, part_fill=None, bounds=(None, None, None)):
-    """lib.rgnn_wgrad_bounds itself, with a partial buffer the caller may pre-fill."""
+    """lib.rgnn_wgrad itself, with a partial buffer the caller may pre-fill."""
     from radargnn_amd._lib import lib
     c = d.op.case
     kt = c.k1 + c.k2 + (1 if ones else 0)
@@ -65,9 +65,9 @@ def raw_wgrad(ops, d, ones, part_fill=None, bounds=(None, None, None)):
     dw = torch.full((c.n, kt), 7.0, dtype=torch.float32, device="cuda")
     p = lambda t: None if t is None else t.data_ptr()
     ld = lambda t: 0 if t is None else ops._ld(t)
-    rc = lib.rgnn_wgrad_bounds(p(d.g), ld(d.g), c.n, p(d.a1) if c.k1 else None, ld(d.a1) if c.k1 else 0, c.k1, p(d.a2), ld(d.a2), c.k2,
-                               1 if ones else 0, c.m, p(d.row_index), p(d.m_dev), p(bounds[0]), p(bounds[1]), p(bounds[2]), p(part), p(dw),
-                               ops._stream())
+    rc = lib.rgnn_wgrad(p(d.g), ld(d.g), c.n, p(d.a1) if c.k1 else None, ld(d.a1) if c.k1 else 0, c.k1, p(d.a2), ld(d.a2), c.k2,
+                        1 if ones else 0, c.m, p(d.row_index), p(d.m_dev), p(bounds[0]), p(bounds[1]), p(bounds[2]), p(part), p(dw),
+                        ops._stream())
     assert rc == 0, lib.rgnn_last_error().decode()
     return dw
 
@@ -272,7 +272,7 @@ def test_refusals_and_empties(ops):
 
     def call(ldg=n, nn=n, kk=k1, ones=1, m=4, rows=None, m_dev=None):
         dW = torch.full((n, k1 + 1), 7.0, device="cuda")
-        rc = lib.rgnn_wgrad_bounds(p(G), ldg, nn, p(A), k1, kk, None, 0, 0, ones, m, rows, m_dev, None, None, None, p(part), p(dW), None)
+        rc = lib.rgnn_wgrad(p(G), ldg, nn, p(A), k1, kk, None, 0, 0, ones, m, rows, m_dev, None, None, None, p(part), p(dW), None)
         torch.cuda.synchronize()
         return rc, dW
 

@@ -10,17 +10,47 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _declarations():
+    """{name: (result type, number of top-level parameters)} of every function include/rgnn.h declares."""
+    header = open(os.path.join(REPO, "include", "rgnn.h")).read()
+    code = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)                   # comments first: they hold commas and parentheses
+    code = re.sub(r"^\s*#.*$", " ", code, flags=re.M)
+    decls = {}
+    for res, name, params in re.findall(r"([A-Za-z_][\w\s]*?[\w*])\s*\b(rgnn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", code):
+        res, params = " ".join(res.split()), params.strip()
+        assert name not in decls, f"{name} is declared twice"
+        decls[name] = (res, 0 if params in ("", "void") else params.count(",") + 1)     # (no parameter is a function pointer)
+    return decls
+
+
 def test_c_abi_exports_every_declared_symbol():
     from radargnn_amd import _lib
-    header = open(os.path.join(REPO, "include", "rgnn.h")).read()
-    declared = set(re.findall(r"\b(rgnn_[a-z0-9_]+)\s*\(", header))
-    declared -= {"rgnn_linear_args", "rgnn_grid"}
-    assert declared, "no declarations parsed"
+    declared = _declarations()
+    assert len(declared) > 100, "declarations not parsed"
     missing = [name for name in sorted(declared) if not hasattr(_lib.lib, name)]
     assert not missing, f"librgnn.so does not export: {missing}"
-    unbound = sorted(declared - set(_lib.SIGNATURES))
-    assert not unbound, f"declared in rgnn.h but not bound in _lib.SIGNATURES: {unbound}"
+    assert set(_lib.SIGNATURES) == set(declared), (
+        f"declared in rgnn.h but not bound in _lib.SIGNATURES: {sorted(set(declared) - set(_lib.SIGNATURES))}; "
+        f"bound but not declared: {sorted(set(_lib.SIGNATURES) - set(declared))}")
     assert _lib.lib.rgnn_version().startswith(b"rgnn")
+
+
+def test_c_abi_bindings_match_the_declared_signatures():
+    """A column added to a declaration or to its SIGNATURES row only is undefined behaviour at the first call: the argument counts
+    agree, and so does the kind of the result (a status / size is not dropped, a void is not read)."""
+    import ctypes as C
+    from radargnn_amd import _lib
+    declared = _declarations()
+    kinds = {"void": (None,), "int": (C.c_int32,), "int32_t": (C.c_int32,), "int64_t": (C.c_int64,), "const char*": (C.c_char_p,)}
+    wrong = []
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        res, n_params = declared[name]
+        assert res in kinds, f"{name}: result type {res!r} not understood"
+        if n_params != len(argtypes):
+            wrong.append(f"{name}: {n_params} parameters declared, {len(argtypes)} bound")
+        if restype not in kinds[res]:
+            wrong.append(f"{name}: returns {res}, bound as {restype}")
+    assert not wrong, wrong
 
 
 def test_c_abi_argument_errors_without_gpu():
@@ -36,6 +66,15 @@ def test_c_abi_argument_errors_without_gpu():
     assert _lib.lib.rgnn_mpnn_work_units(3000, 30000) == 16                # one frame: finer chunks, so the chip fills
     rc = _lib.lib.rgnn_linear_fwd(None, None)
     assert rc == -1 and b"null args" in _lib.lib.rgnn_last_error()
+    # checks that moved into the one export of a family; each returns before any launch (the addresses are never dereferenced)
+    import ctypes as C
+    dummy = C.addressof((C.c_int32 * 4)())
+    for perm, own in ((dummy, dummy), (None, None)):                         # with edges: exactly one of perm / own_edge
+        rc = _lib.lib.rgnn_csr_by_target_symmetric(dummy, dummy, 4, 2, None, dummy, dummy, perm, own, dummy, None, None)
+        assert rc == -1 and b"exactly one of perm / own_edge" in _lib.lib.rgnn_last_error()
+    rc = _lib.lib.rgnn_mpnn_aggregate_max_arg(None, dummy, 8, None, 0, None, 0, dummy, dummy, None, None, 0, 4, 8, dummy, 8, dummy, 0,
+                                              None, None, None)
+    assert rc == -1 and b"null arg_written" in _lib.lib.rgnn_last_error()
 
 
 def test_state_dict_keys_match_the_reference_contract():

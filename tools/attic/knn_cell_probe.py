@@ -31,7 +31,7 @@ def main():
             g = ops.GridHash(b.X, b.frame_ptr).build(cell_size=0.0, pts_per_cell=ppc, max_frame_points=biggest)
             n = g.n
             nbr = torch.full((n, k), -7, dtype=torch.int32, device="cuda")
-            ops.check(lib.rgnn_knn_graph(C.byref(g.desc), k, ops._ptr(nbr), None, ops._ptr(st), ops._stream()))
+            ops.check(lib.rgnn_knn_graph(C.byref(g.desc), k, 0, ops._ptr(nbr), None, ops._ptr(st), None, 0, None, ops._stream()))
             torch.cuda.synchronize()
             if ref is None:
                 ref = nbr.clone()
@@ -44,7 +44,7 @@ def main():
                 e1.record(); torch.cuda.synchronize(); tg.append(e0.elapsed_time(e1) / 5)
                 e0.record()
                 for _ in range(5):
-                    lib.rgnn_knn_graph(C.byref(g.desc), k, ops._ptr(nbr), None, ops._ptr(st), ops._stream())
+                    lib.rgnn_knn_graph(C.byref(g.desc), k, 0, ops._ptr(nbr), None, ops._ptr(st), None, 0, None, ops._stream())
                 e1.record(); torch.cuda.synchronize(); ts.append(e0.elapsed_time(e1) / 5)
             ts.sort(); tg.sort()
             print(f"    pts_per_cell {ppc:5.1f}: search {ts[len(ts) // 2] * 1e3:8.1f} us, grid build {tg[len(tg) // 2] * 1e3:6.1f} us, "

@@ -32,7 +32,7 @@ def main():
             __import__("radargnn_amd").ops.reload_env()
             nbr = torch.full((n, k), -7, dtype=torch.int32, device="cuda")
             ei = torch.full((2, n * k), -7, dtype=torch.int64, device="cuda")
-            ops.check(lib.rgnn_knn_graph(C.byref(g.desc), k, ops._ptr(nbr), ops._ptr(ei), ops._ptr(st), ops._stream()))
+            ops.check(lib.rgnn_knn_graph(C.byref(g.desc), k, 0, ops._ptr(nbr), ops._ptr(ei), ops._ptr(st), None, 0, None, ops._stream()))
             torch.cuda.synchronize()
             outs.append((nbr, ei))
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -41,10 +41,10 @@ def main():
             for v in variants:
                 os.environ["RGNN_KNN_TEAM"] = v
                 __import__("radargnn_amd").ops.reload_env()
-                lib.rgnn_knn_graph(C.byref(g.desc), k, ops._ptr(nbr), None, ops._ptr(st), ops._stream())
+                lib.rgnn_knn_graph(C.byref(g.desc), k, 0, ops._ptr(nbr), None, ops._ptr(st), None, 0, None, ops._stream())
                 e0.record()
                 for _ in range(5):
-                    lib.rgnn_knn_graph(C.byref(g.desc), k, ops._ptr(nbr), None, ops._ptr(st), ops._stream())
+                    lib.rgnn_knn_graph(C.byref(g.desc), k, 0, ops._ptr(nbr), None, ops._ptr(st), None, 0, None, ops._stream())
                 e1.record()
                 torch.cuda.synchronize()
                 times[v].append(e0.elapsed_time(e1) / 5)

@@ -71,7 +71,7 @@ def main():
             assert lib.rgnn_mpnn_partition(ptr(csr.rowptr), n, e, ptr(chunks), stream) == 0
             run.done.add(i)
         rc = lib.rgnn_mpnn_aggregate(None, 0, None, ptr(Q), d, ptr(We), 8, ptr(ea), 8, ptr(csr.rowptr), ptr(csr.src),
-                                     ptr(csr.order), ptr(chunks), nc, n, d, aggr, ptr(out), d, stream)
+                                     ptr(csr.order), ptr(chunks), nc, n, d, aggr, ptr(out), d, 0, None, stream)
         for k, _ in envs:
             os.environ.pop(k, None)
             __import__("radargnn_amd").ops.reload_env()

@@ -121,12 +121,12 @@ def main():
 
     def new(out):
         _lib.check(lib.rgnn_mpnn_aggregate_win(ptr(bias), ptr(Q), d, ptr(We), 8, ptr(ea), 8, ptr(csr.rowptr), ptr(csr.src), ptr(csr.order),
-                                               ptr(dplan), n, e, d, ptr(out), d, 1, None, stream))
+                                               ptr(dplan), n, e, d, ptr(out), d, 1, None, None, stream))
 
     def old(out):
-        _lib.check(lib.rgnn_mpnn_aggregate_absmax(None, 0, ptr(bias), ptr(Q), d, ptr(We), 8, ptr(ea), 8, ptr(csr.rowptr), ptr(csr.src),
-                                                  ptr(csr.order), ptr(csr.chunks), lib.rgnn_mpnn_num_chunks(n, e), n, d, 0, ptr(out), d,
-                                                  1, None, stream))
+        _lib.check(lib.rgnn_mpnn_aggregate(None, 0, ptr(bias), ptr(Q), d, ptr(We), 8, ptr(ea), 8, ptr(csr.rowptr), ptr(csr.src),
+                                           ptr(csr.order), ptr(csr.chunks), lib.rgnn_mpnn_num_chunks(n, e), n, d, 0, ptr(out), d,
+                                           1, None, stream))
 
     oa = torch.full((n, d), 7.0, device="cuda"); ob = torch.full((n, d), 7.0, device="cuda")
     old(oa); new(ob)
