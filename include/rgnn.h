@@ -1000,6 +1000,90 @@ int rgnn_nusc_label_points(const double* pos, int64_t n, const int64_t* frame_pt
                            int32_t invariance, double wlh_offset, int32_t* label, double* out, int32_t* hit /*[dev] or NULL*/,
                            int32_t* status /*[dev]*/, rgnn_stream_t stream);
 
+/* ---------------------------------------------------------------- nuScenes detection evaluation (csrc/nuscenes_eval.hip)
+ * What the reference's NuscenesEvaluator runs after the post-processor (postprocessor/nuscenes/evaluation.py:41-74): the submission
+ * records (postprocessor/nuscenes/utils.py:11-140,246-309) and the devkit's DetectionEval (eval/common/loaders.py add_center_dist /
+ * filter_eval_boxes, eval/detection/algo.py accumulate / calc_ap / calc_tp, eval/common/utils.py center_distance / scale_iou /
+ * yaw_diff / angle_diff / cummean).  float64, no fused multiply-add.  NOT PINNED BY AN EXECUTED DEVKIT: the semantics are restated
+ * from the published sources (see the head of csrc/nuscenes_eval.hip); tests hold the kernels to a numpy restatement of the same
+ * statements.  Every function clears its own status word ([dev] int32) and ORs the bits below into it; the caller reads it once.
+ *
+ * Names are int32 codes into the reference's label list (utils.py:172-184: 0 'void', 1 'barrier', 2 'bicycle', 3 'bus', 4 'car',
+ * 5 'construction_vehicle', 6 'motorcycle', 7 'pedestrian', 8 'traffic_cone', 9 'trailer', 10 'truck'); attributes are int32 codes
+ * the caller chooses, a negative one standing for ''.
+ *
+ * rgnn_nuscenes_submission (utils.py:246-309), one thread per box.  boxes [n_boxes, 5] = (x, y, l, w, theta in degrees) in the
+ * vehicle frame (rgnn_box_representations), labels int32, sample s owning [box_ptr[s], box_ptr[s + 1]) with the LIDAR_TOP ego pose
+ * ego_translation [n_samples, 3] / ego_rotation [n_samples, 4] (w, x, y, z; normalised here); heights [n_heights] by label
+ * (get_bounding_box_size).  translation = R (x, y, 0) + t_e with z raised by h / 2; size = (w, l, h); angle = theta pi / 180 + yaw_e
+ * with yaw_e = atan2(2 (w z - x y), 1 - 2 (y^2 + z^2)) (pyquaternion's yaw_pitch_roll[0]); rotation = (cos(angle / 2), 0, 0,
+ * sin(angle / 2)); yaw = angle.  A label < 1 or >= n_heights raises RGNN_NUSC_EVAL_BAD_LABEL and its rows stay unwritten.
+ *
+ * rgnn_detection_filter (add_center_dist, filter_eval_boxes), one thread per box, for predictions (score given, num_pts NULL) and
+ * ground truth (num_pts given, score NULL) alike.  keep uint8 [n_boxes] = sqrt(dx^2 + dy^2) of translation - ego_translation is
+ * strictly below class_range[name], and num_pts > 0 where given, and -- for the names `bicycle` / `motorcycle`, where rack_ptr
+ * (int64 [n_samples + 1]) is given -- the centre lies in no bike-rack box of the sample (the devkit's points_in_box: the
+ * projections on the three edges of corner 0 lie in [0, |edge|^2], ends included; rack_size = w, l, h).  A name < 1 or >= n_names
+ * is dropped and, for a prediction, raises RGNN_NUSC_EVAL_BAD_LABEL.  max_boxes > 0: a sample with more boxes raises
+ * RGNN_NUSC_EVAL_TOO_MANY_BOXES (the devkit's assert); a NaN score raises RGNN_NUSC_EVAL_NAN_SCORE.
+ *
+ * rgnn_center_match (accumulate's loop), one wave per (sample, class of `classes`, threshold).  order: [dev] int64 [pred.n], the
+ * predictions sample by sample, inside a sample by descending score with equal scores by DESCENDING position (the devkit sorts
+ * (score, index) ascending and reverses): rgnn_sort_scores on the reversed array, then a stable pass by sample.  Per prediction of
+ * the class that the filter kept, in that order: the minimum xy centre distance over the sample's kept ground truth of the class
+ * not yet taken at this threshold, lowest position on ties; matched iff it is strictly below the threshold.  Thresholds are
+ * independent passes.  match: int32 [n_thresholds, pred.n], the ground-truth box's index or -1; tp_err: [5, pred.n] for threshold
+ * tp_index only -- centre distance, 1 - scale IoU, |yaw difference| (period 2 pi, pi for the name `barrier`), xy velocity
+ * difference, attribute error (NaN for a ground-truth attribute < 0, else 0 / 1) -- NaN where unmatched.  Both are cleared here.
+ * Capacity: rgnn_center_match_capacity() (512) kept ground-truth boxes of ONE class in one sample, counted on the device: more
+ * raise RGNN_NUSC_EVAL_GT_OVERFLOW and leave that pair unmatched.  Offsets outside the lists raise RGNN_NUSC_EVAL_BAD_PTR.
+ *
+ * rgnn_detection_curves (accumulate after the loop, cummean), one work-group per (class, threshold).  order: [dev] int64, the KEPT
+ * predictions class by class in the order of `classes`, inside a class by descending score over all samples (equal scores by
+ * descending position); cls_ptr: int64 [2, n_classes], where each class begins and ends in it.  npos = the class's kept ground
+ * truth.  npos == 0 or no match at the threshold: precision 0, confidence 0, errors 1.  Otherwise tp = running count of matches,
+ * prec = tp / (tp + fp), rec = tp / npos, and precision / confidence = np.interp(grid, rec, ., right = 0): the LAST j with
+ * rec[j] <= x; x < rec[0] gives the first value; j last or rec[j] == x gives value j; else (f[j+1] - f[j]) / (rec[j+1] - rec[j])
+ * (x - rec[j]) + f[j].  For threshold tp_index, each error's running mean over the matched predictions that are not NaN (0
+ * before the first, all ones if every value is NaN) is resampled at the interpolated confidence by np.interp over the reversed
+ * arrays.  precision, confidence: [n_classes, n_thresholds, n_grid]; tp_err_curve: [n_classes, 5, n_grid]; grid: [n_grid]
+ * ascending (at most 128); tmp: [dev] rgnn_detection_curves_tmp_bytes(n_pred, n_thresholds) bytes. */
+#define RGNN_NUSC_EVAL_BAD_LABEL 1
+#define RGNN_NUSC_EVAL_TOO_MANY_BOXES 2
+#define RGNN_NUSC_EVAL_NAN_SCORE 4
+#define RGNN_NUSC_EVAL_GT_OVERFLOW 8
+#define RGNN_NUSC_EVAL_BAD_PTR 16
+typedef struct rgnn_eval_boxes {
+  const double* translation; /* [n, 3] global frame                */
+  const double* size;        /* [n, 3] w, l, h                     */
+  const double* rotation;    /* [n, 4] w, x, y, z                  */
+  const double* velocity;    /* [n, 2] may be NaN                  */
+  const int32_t* name;       /* [n]                                */
+  const int32_t* attribute;  /* [n] negative: ''                   */
+  const uint8_t* keep;       /* [n] rgnn_detection_filter          */
+  const int64_t* ptr;        /* [n_samples + 1]                    */
+  int64_t n;
+} rgnn_eval_boxes;
+int rgnn_nuscenes_submission(const double* boxes, const int32_t* labels, int64_t n_boxes, const int64_t* box_ptr, int64_t n_samples,
+                             const double* ego_translation, const double* ego_rotation, const double* heights, int32_t n_heights,
+                             double* translation, double* size, double* rotation, double* yaw, int32_t* status, rgnn_stream_t stream);
+int rgnn_detection_filter(const double* translation, const int32_t* name, int64_t n_boxes, const int64_t* ptr, int64_t n_samples,
+                          const double* ego_translation, const double* class_range, int32_t n_names,
+                          const int32_t* num_pts /*[dev] or NULL*/, const double* score /*[dev] or NULL*/, int32_t max_boxes,
+                          const double* rack_center, const double* rack_size, const double* rack_rotation,
+                          const int64_t* rack_ptr /*[dev] or NULL*/, int64_t n_racks, int32_t bicycle, int32_t motorcycle,
+                          uint8_t* keep, int32_t* status, rgnn_stream_t stream);
+int32_t rgnn_center_match_capacity(void);
+int rgnn_center_match(const rgnn_eval_boxes* pred, const rgnn_eval_boxes* gt, int64_t n_samples, const int64_t* order,
+                      const int32_t* classes, int32_t n_classes, const double* thresholds, int32_t n_thresholds, int32_t tp_index,
+                      int32_t barrier, int32_t* match, double* tp_err, int32_t* status, rgnn_stream_t stream);
+int64_t rgnn_detection_curves_tmp_bytes(int64_t n_pred, int32_t n_thresholds);
+int rgnn_detection_curves(const int64_t* order, const int64_t* cls_ptr, const double* score, const int32_t* match,
+                          const double* tp_err, int64_t n_pred, const int32_t* gt_name, const uint8_t* gt_keep, int64_t n_gt,
+                          const int32_t* classes, int32_t n_classes, int32_t n_thresholds, int32_t tp_index, const double* grid,
+                          int32_t n_grid, double* precision, double* confidence, double* tp_err_curve, void* tmp,
+                          rgnn_stream_t stream);
+
 /* ---------------------------------------------------------------- optimizer step and target re-encoding (csrc/optim.hip)
  * rgnn_adam_step: torch.optim.Adam with amsgrad and maximize off and the weight decay added to the gradient, for n_tensors float32
  * tensors at once.  The tables are HOST arrays of length n_tensors, read before the call returns: device pointers of the parameter,

@@ -37,6 +37,11 @@ class RgnnLinearArgs(C.Structure):
                 ("W_planes_f16", c_vp), ("a1_bound", c_vp), ("a2_bound", c_vp), ("out_absmax", c_vp), ("a1_panel_segment", c_vp)]
 
 
+class RgnnEvalBoxes(C.Structure):
+    _fields_ = [("translation", c_vp), ("size", c_vp), ("rotation", c_vp), ("velocity", c_vp), ("name", c_vp), ("attribute", c_vp),
+                ("keep", c_vp), ("ptr", c_vp), ("n", c_i64)]
+
+
 # name -> (restype, argtypes); one entry per function declared in include/rgnn.h
 SIGNATURES = {
     "rgnn_version": (C.c_char_p, []),
@@ -186,6 +191,15 @@ SIGNATURES = {
                                 c_vp, c_vp]),
     "rgnn_nusc_label_points": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_f64, c_vp, c_vp, c_vp, c_vp,
                                        c_vp]),
+    "rgnn_nuscenes_submission": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_detection_filter": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                      c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "rgnn_center_match_capacity": (c_i32, []),
+    "rgnn_center_match": (c_i32, [C.POINTER(RgnnEvalBoxes), C.POINTER(RgnnEvalBoxes), c_i64, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32,
+                                  c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_detection_curves_tmp_bytes": (c_i64, [c_i64, c_i32]),
+    "rgnn_detection_curves": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rgnn_adam_capacity": (c_i32, []),
     "rgnn_adam_step": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, C.POINTER(c_i32), c_vp]),
     "rgnn_adapt_orientation_angle": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp]),

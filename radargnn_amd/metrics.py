@@ -12,7 +12,8 @@ Differences from the reference, all deliberate:
   * an empty first frame does not raise; the kind of the boxes comes from ``BoundingBoxes.is_aligned``;
   * equal scores go by ascending position (the reference's ``torch.sort`` leaves ties unpinned);
   * the aligned box IoU restates ``torchvision.ops.box_iou`` and is not pinned by an executed torchvision;
-  * ``"nuscenes"`` is absent from ``evaluation_selector`` (its evaluator needs the nuscenes-devkit); no confusion plot is written.
+  * ``"nuscenes"`` is absent from THIS ``evaluation_selector``: the nuScenes evaluator lives in ``radargnn_amd.nuscenes_eval``, whose own
+    ``evaluation_selector`` holds both keys (it needs ground truth this module's callers do not have); no confusion plot is written.
 """
 from __future__ import annotations
 

@@ -17,9 +17,9 @@ one launch that prepares the boxes, one launch that gives every point its label 
 same point-in-box mask twice, once for each.  One host read in the point stage (``frame_ptr`` with the status word); the points
 never return to the host.  There is no CPU path.
 
-Out of scope, on purpose: reading the dataset (``NuScenes(...)``, ``from_file_multisweep``, the split lists), the nuScenes
-evaluator, and the class-name -> id table (``_get_box_label`` is a list of names; ``box_label`` comes from the caller as integers,
-as ``preprocessor.py`` takes ``label_map`` without a default).
+The nuScenes evaluator (submission records, NDS, mAP) is ``radargnn_amd.nuscenes_eval``.  Out of scope, on purpose: reading the
+dataset (``NuScenes(...)``, ``from_file_multisweep``, the split lists) and the class-name -> id table (``_get_box_label`` is a
+list of names; ``box_label`` comes from the caller as integers, as ``preprocessor.py`` takes ``label_map`` without a default).
 
 Layout.  ``points`` is float64 [19, N_total], channel-major: the devkit's 18 radar channels with the timestamp row beneath, exactly
 what ``get_sensor_points`` stacks (dataset_creation.py:183), in the SENSOR frame.  It is laid out in chunks, one per (sample,

@@ -2410,3 +2410,161 @@ def adapt_orientation_angle(y: torch.Tensor) -> torch.Tensor:
     n, w = y.shape
     check(lib.rgnn_adapt_orientation_angle(_ptr(y), _ld(y) if n > 1 else w, _ptr(out), w, n, w, _stream()))
     return out
+
+
+# ---- nuScenes detection evaluation (csrc/nuscenes_eval.hip) ------------------------------------------------------------
+STATUS_NUSC_EVAL_BAD_LABEL = 1
+STATUS_NUSC_EVAL_TOO_MANY_BOXES = 2
+STATUS_NUSC_EVAL_NAN_SCORE = 4
+STATUS_NUSC_EVAL_GT_OVERFLOW = 8
+STATUS_NUSC_EVAL_BAD_PTR = 16
+
+
+def _f64(t, name, shape_tail=None):
+    t = _dev(t, name, torch.float64).contiguous()
+    return t if shape_tail is None else t.reshape(-1, shape_tail)
+
+
+def nuscenes_submission(boxes: torch.Tensor, labels: torch.Tensor, box_ptr: torch.Tensor, ego_translation: torch.Tensor,
+                        ego_rotation: torch.Tensor, heights: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """Submission geometry of every predicted box in one launch (rgnn_nuscenes_submission) -> (translation f64 [M, 3], size f64
+    [M, 3] = (w, l, h), rotation f64 [M, 4], global yaw f64 [M], status int32 [1] on the device).  ``boxes`` f64 [M, 5] from
+    ``box_representations``, ``labels`` int32 [M], ``box_ptr`` int64 [S + 1], the ego pose per sample, ``heights`` f64 by label.
+    ``out``: a flat f64 buffer of at least 11 M elements that receives the four outputs back to back.  The caller reads the status
+    word (STATUS_NUSC_EVAL_BAD_LABEL)."""
+    boxes = _f64(boxes, "boxes", 5)
+    labels = _dev(labels, "labels", torch.int32).contiguous()
+    box_ptr = _dev(box_ptr, "box_ptr", torch.int64).contiguous()
+    ego_t, ego_r, heights = _f64(ego_translation, "ego_translation", 3), _f64(ego_rotation, "ego_rotation", 4), _f64(heights, "heights")
+    m, s = boxes.shape[0], box_ptr.numel() - 1
+    if labels.shape != (m,) or s < 0 or ego_t.shape[0] != s or ego_r.shape[0] != s:
+        raise ValueError("one label per box; box_ptr [S + 1], ego_translation [S, 3], ego_rotation [S, 4]")
+    if out is None:
+        out = torch.empty(11 * m, dtype=torch.float64, device=boxes.device)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < 11 * m or out.device != boxes.device:
+        raise ValueError("out must be a contiguous float64 buffer of at least 11 M elements on the boxes' device")
+    translation, size = out[:3 * m].view(m, 3), out[3 * m:6 * m].view(m, 3)
+    rotation, yaw = out[6 * m:10 * m].view(m, 4), out[10 * m:11 * m]
+    status = torch.empty(1, dtype=torch.int32, device=boxes.device)
+    check(lib.rgnn_nuscenes_submission(_ptr(boxes), _ptr(labels), m, _ptr(box_ptr), s, _ptr(ego_t), _ptr(ego_r), _ptr(heights),
+                                       heights.numel(), _ptr(translation), _ptr(size), _ptr(rotation), _ptr(yaw), _ptr(status),
+                                       _stream()))
+    return translation, size, rotation, yaw, status
+
+
+def detection_filter(translation: torch.Tensor, name: torch.Tensor, ptr: torch.Tensor, ego_translation: torch.Tensor,
+                     class_range: torch.Tensor, bicycle: int, motorcycle: int, num_pts: Optional[torch.Tensor] = None,
+                     score: Optional[torch.Tensor] = None, max_boxes: int = 0, racks=None):
+    """The devkit's range / point-count / bike-rack filter in one launch (rgnn_detection_filter) -> (keep uint8 [N], status int32
+    [1] on the device).  Predictions pass ``score`` (f64) and ``max_boxes``; ground truth passes ``num_pts`` (int32).  ``racks``:
+    None or (center f64 [R, 3], size f64 [R, 3], rotation f64 [R, 4], ptr int64 [S + 1])."""
+    translation = _f64(translation, "translation", 3)
+    name = _dev(name, "name", torch.int32).contiguous()
+    ptr = _dev(ptr, "ptr", torch.int64).contiguous()
+    ego_t, class_range = _f64(ego_translation, "ego_translation", 3), _f64(class_range, "class_range")
+    n, s = translation.shape[0], ptr.numel() - 1
+    if name.shape != (n,) or s < 0 or ego_t.shape[0] != s:
+        raise ValueError("one name per box; ptr [S + 1], ego_translation [S, 3]")
+    if num_pts is not None:
+        num_pts = _dev(num_pts, "num_pts", torch.int32).contiguous()
+    if score is not None:
+        score = _f64(score, "score")
+    if (num_pts is not None and num_pts.shape != (n,)) or (score is not None and score.shape != (n,)):
+        raise ValueError("one num_pts / score per box")
+    rc = rs = rr = rp = None
+    n_racks = 0
+    if racks is not None:
+        rc, rs, rr = _f64(racks[0], "rack centre", 3), _f64(racks[1], "rack size", 3), _f64(racks[2], "rack rotation", 4)
+        rp = _dev(racks[3], "rack ptr", torch.int64).contiguous()
+        n_racks = rc.shape[0]
+        if rs.shape[0] != n_racks or rr.shape[0] != n_racks or rp.shape != (s + 1,):
+            raise ValueError("racks: centre / size [R, 3], rotation [R, 4], ptr [S + 1]")
+    keep = torch.empty(n, dtype=torch.uint8, device=translation.device)
+    status = torch.empty(1, dtype=torch.int32, device=translation.device)
+    check(lib.rgnn_detection_filter(_ptr(translation), _ptr(name), n, _ptr(ptr), s, _ptr(ego_t), _ptr(class_range), class_range.numel(),
+                                    _ptr(num_pts), _ptr(score), int(max_boxes), _ptr(rc), _ptr(rs), _ptr(rr), _ptr(rp), n_racks,
+                                    int(bicycle), int(motorcycle), _ptr(keep), _ptr(status), _stream()))
+    return keep, status
+
+
+def center_match_capacity() -> int:
+    """Kept ground-truth boxes of one class in one sample ``center_match`` holds (rgnn_center_match_capacity)."""
+    return int(lib.rgnn_center_match_capacity())
+
+
+def _eval_boxes(b: dict, what: str):
+    """dict of device tensors -> (RgnnEvalBoxes, the tensors it points into)."""
+    n = b["translation"].shape[0]
+    hold = [_f64(b["translation"], what + " translation", 3), _f64(b["size"], what + " size", 3), _f64(b["rotation"], what + " rotation", 4),
+            _f64(b["velocity"], what + " velocity", 2), _dev(b["name"], what + " name", torch.int32).contiguous(),
+            _dev(b["attribute"], what + " attribute", torch.int32).contiguous(), _dev(b["keep"], what + " keep", torch.uint8).contiguous(),
+            _dev(b["ptr"], what + " ptr", torch.int64).contiguous()]
+    if any(t.shape[0] != n for t in hold[:7]):
+        raise ValueError(f"{what}: translation / size [N, 3], rotation [N, 4], velocity [N, 2], name / attribute / keep [N]")
+    return _lib.RgnnEvalBoxes(*[t.data_ptr() if t.numel() else None for t in hold], n), hold
+
+
+def sample_score_order(score: torch.Tensor, ptr: torch.Tensor) -> torch.Tensor:
+    """int64 [M]: the predictions sample by sample, inside a sample by descending score, equal scores by DESCENDING position (the
+    devkit's ``sorted((score, index))[::-1]``): rgnn_sort_scores on the reversed array, then a stable pass by sample."""
+    score = _f64(score, "score")
+    m = score.numel()
+    order = (m - 1) - sort_scores(score.flip(0))
+    sample = torch.searchsorted(ptr, order, right=True) - 1
+    return order.index_select(0, sort_scores(-sample.to(torch.float64)))
+
+
+def center_match(pred: dict, gt: dict, order: torch.Tensor, classes: torch.Tensor, thresholds: Sequence[float], tp_index: int,
+                 barrier: int):
+    """The devkit's greedy centre-distance matching of every (sample, class, threshold) in one launch (rgnn_center_match) ->
+    (match int32 [T, M]: the ground-truth box's index or -1, tp_err f64 [5, M] for threshold ``tp_index``, status int32 [1] on the
+    device).  ``pred`` / ``gt``: dicts of device tensors translation, size, rotation, velocity, name, attribute, keep, ptr;
+    ``order`` from ``sample_score_order``."""
+    pb, hold_p = _eval_boxes(pred, "pred")
+    gb, hold_g = _eval_boxes(gt, "gt")
+    s = hold_p[7].numel() - 1
+    if s < 0 or hold_g[7].numel() != s + 1:
+        raise ValueError("pred and gt need the same number of samples")
+    dev = hold_p[0].device
+    order = _dev(order, "order", torch.int64).contiguous()
+    classes = _dev(classes, "classes", torch.int32).contiguous()
+    thr = torch.tensor([float(t) for t in thresholds], dtype=torch.float64).to(dev)
+    m = pb.n
+    if order.shape != (m,):
+        raise ValueError("order needs one entry per prediction")
+    match = torch.empty((thr.numel(), m), dtype=torch.int32, device=dev)
+    tp_err = torch.empty((5, m), dtype=torch.float64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib.rgnn_center_match(C.byref(pb), C.byref(gb), s, _ptr(order), _ptr(classes), classes.numel(), _ptr(thr), thr.numel(),
+                                int(tp_index), int(barrier), _ptr(match), _ptr(tp_err), _ptr(status), _stream()))
+    return match, tp_err, status
+
+
+def detection_curves(order: torch.Tensor, cls_ptr: torch.Tensor, score: torch.Tensor, match: torch.Tensor, tp_err: torch.Tensor,
+                     gt_name: torch.Tensor, gt_keep: torch.Tensor, classes: torch.Tensor, tp_index: int, grid: torch.Tensor):
+    """The devkit's precision / confidence / TP-error tables, one work-group per (class, threshold) (rgnn_detection_curves) ->
+    (precision f64 [C, T, R], confidence f64 [C, T, R], tp_err_curve f64 [C, 5, R]).  ``order``: the kept predictions class by
+    class, inside a class by descending score (ties by descending position); ``cls_ptr`` int64 [2, C]; ``grid`` f64 [R]."""
+    order = _dev(order, "order", torch.int64).contiguous()
+    cls_ptr = _dev(cls_ptr, "cls_ptr", torch.int64).contiguous()
+    score = _f64(score, "score")
+    match = _dev(match, "match", torch.int32).contiguous()
+    tp_err = _dev(tp_err, "tp_err", torch.float64).contiguous()
+    gt_name = _dev(gt_name, "gt_name", torch.int32).contiguous()
+    gt_keep = _dev(gt_keep, "gt_keep", torch.uint8).contiguous()
+    classes = _dev(classes, "classes", torch.int32).contiguous()
+    grid = _f64(grid, "grid")
+    m, c, dev = score.numel(), classes.numel(), score.device
+    if match.dim() != 2 or match.shape[1] != m or tp_err.shape != (5, m) or cls_ptr.shape != (2, c) or order.numel() > m:
+        raise ValueError("match [T, M], tp_err [5, M], cls_ptr [2, C]; order lists at most M predictions")
+    if gt_name.shape != gt_keep.shape:
+        raise ValueError("one keep flag per ground-truth box")
+    t, r = match.shape[0], grid.numel()
+    precision = torch.empty((c, t, r), dtype=torch.float64, device=dev)
+    confidence = torch.empty((c, t, r), dtype=torch.float64, device=dev)
+    tp_curve = torch.empty((c, 5, r), dtype=torch.float64, device=dev)
+    tmp = torch.empty(max(int(lib.rgnn_detection_curves_tmp_bytes(m, t)), 8), dtype=torch.uint8, device=dev)
+    check(lib.rgnn_detection_curves(_ptr(order), _ptr(cls_ptr), _ptr(score), _ptr(match), _ptr(tp_err), m, _ptr(gt_name), _ptr(gt_keep),
+                                    gt_name.numel(), _ptr(classes), c, t, int(tp_index), _ptr(grid), r, _ptr(precision),
+                                    _ptr(confidence), _ptr(tp_curve), _ptr(tmp), _stream()))
+    return precision, confidence, tp_curve
