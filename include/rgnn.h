@@ -644,6 +644,18 @@ int rgnn_gather_rows_f32(const float* in, int64_t ldi, const int32_t* perm, int6
 /* Row softmax of the class logits (postprocessor/inference.py:46,62). */
 int rgnn_softmax_rows(const float* x, int64_t ldx, int64_t m, int32_t n, float* y, int64_t ldy, rgnn_stream_t stream);
 
+/* The epilogue of one prediction step (postprocessor/inference.py:51-68) in one launch, for the rows r < n of the step:
+ *   prob[r, :n_classes]        = softmax(cls[r, :n_classes])   -- the statements of rgnn_softmax_rows: bit-equal to it
+ *   bb_out[r, :box_width]      = bb[r, :box_width]
+ *   class_true[r]              = y[r, 0]                       -- y: float32 or float64 (y_is_f64), moved word for word
+ *   bb_true[r, :target_width]  = y[r, 1 : 1 + target_width]
+ * The outputs are rows of whole-split buffers: the caller passes their pointers advanced to the step's first row.  Leading
+ * dimensions count elements of the matrix's own type (ldy and ldt: of y's).  y may be NULL: class_true and bb_true are then
+ * not touched.  n == 0 returns RGNN_OK without a launch. */
+int rgnn_predict_rows(const float* cls, int64_t ldc, int32_t n_classes, const float* bb, int64_t ldb, int32_t box_width,
+                      const void* y, int64_t ldy, int32_t y_is_f64, int32_t target_width, int64_t n, float* prob, int64_t ldp,
+                      float* bb_out, int64_t ldo, void* class_true, void* bb_true, int64_t ldt, rgnn_stream_t stream);
+
 /* ================================================================ batches of graphs resident in HBM
  * Device-side replacement of torch_geometric's DataLoader collation (utils/data_handling.py:30 -> Batch.from_data_list)
  * and of the per-batch host-to-device copy (postprocessor/inference.py:57): the processed dataset lives in HBM as

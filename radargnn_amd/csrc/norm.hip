@@ -573,6 +573,42 @@ __global__ __launch_bounds__(256) void k_softmax_rows(const float* __restrict__ 
   for (int c = 0; c < n; c++) y[r * ldy + c] = expf(xr[c] - mx) / s;
 }
 
+// The epilogue of a prediction step (postprocessor/inference.py:51-68; radargnn_amd/inference.py) in one launch: the softmax of the
+// class logits, the boxes, and the two halves of y, each written at the step's rows of a whole-split buffer.  The softmax is
+// k_softmax_rows statement for statement (one thread per row: the same bits); the copies run over a flat element index of the
+// block's 256 rows, so consecutive lanes move consecutive words of rows that are 4 .. 6 words long (a thread per row would touch a
+// word of every 16 .. 48 bytes).  Word = the 4- or 8-byte pattern of y's dtype: moved as integers, so every NaN payload survives.
+template <typename Word>
+__global__ __launch_bounds__(256) void k_predict_rows(const float* __restrict__ cls, int64_t ldc, int n_classes,
+                                                     const uint32_t* __restrict__ bb, int64_t ldb, int box_width,
+                                                     const Word* __restrict__ y, int64_t ldy, int target_width, int64_t n,
+                                                     float* __restrict__ prob, int64_t ldp, uint32_t* __restrict__ bb_out, int64_t ldo,
+                                                     Word* __restrict__ class_true, Word* __restrict__ bb_true, int64_t ldt) {
+  const int64_t row0 = (int64_t)blockIdx.x * 256;
+  const int64_t r = row0 + threadIdx.x;
+  if (r < n) {
+    const float* xr = cls + r * ldc;
+    float mx = -INFINITY;
+    for (int c = 0; c < n_classes; c++) mx = fmaxf(mx, xr[c]);
+    float s = 0.f;
+    for (int c = 0; c < n_classes; c++) s += expf(xr[c] - mx);
+    for (int c = 0; c < n_classes; c++) prob[r * ldp + c] = expf(xr[c] - mx) / s;
+  }
+  const int rows = (int)(n - row0 < 256 ? n - row0 : 256);
+  for (int i = threadIdx.x; i < rows * box_width; i += 256) {
+    const int rr = i / box_width, c = i - rr * box_width;
+    bb_out[(row0 + rr) * ldo + c] = bb[(row0 + rr) * ldb + c];
+  }
+  if (y == nullptr) return;
+  const int wy = 1 + target_width;
+  for (int i = threadIdx.x; i < rows * wy; i += 256) {
+    const int rr = i / wy, c = i - rr * wy;
+    const Word v = y[(row0 + rr) * ldy + c];
+    if (c == 0) class_true[row0 + rr] = v;
+    else bb_true[(row0 + rr) * ldt + (c - 1)] = v;
+  }
+}
+
 // Backward coefficients of BatchNorm1d (+ fused ReLU) for rgnn_bn_bwd_apply, one launch instead of a dozen [C]-sized
 // float64 tensor operations: from the forward column statistics (or the running statistics in eval mode) and the backward
 // partial sums (sum g, sum g h per panel; g = relu'(y) dy):
@@ -866,6 +902,28 @@ extern "C" int rgnn_softmax_rows(const float* x, int64_t ldx, int64_t m, int32_t
   if (m == 0 || n == 0) return RGNN_OK;
   RGNN_CHECK_ARG(x && y, "null pointers");
   hipLaunchKernelGGL(k_softmax_rows, dim3(rgnn_blocks(m, 256)), dim3(256), 0, (hipStream_t)stream, x, ldx, m, n, y, ldy);
+  RGNN_CHECK_LAUNCH();
+  return RGNN_OK;
+}
+
+extern "C" int rgnn_predict_rows(const float* cls, int64_t ldc, int32_t n_classes, const float* bb, int64_t ldb, int32_t box_width,
+                                 const void* y, int64_t ldy, int32_t y_is_f64, int32_t target_width, int64_t n, float* prob,
+                                 int64_t ldp, float* bb_out, int64_t ldo, void* class_true, void* bb_true, int64_t ldt,
+                                 rgnn_stream_t stream) {
+  RGNN_CHECK_ARG(n >= 0 && n_classes >= 1 && box_width >= 0 && target_width >= 0, "bad sizes");
+  RGNN_CHECK_ARG(ldc >= 0 && ldb >= 0 && ldy >= 0 && ldp >= 0 && ldo >= 0 && ldt >= 0, "negative leading dimension");
+  if (n == 0) return RGNN_OK;
+  RGNN_CHECK_ARG(cls && prob && (box_width == 0 || (bb && bb_out)), "null pointers");
+  RGNN_CHECK_ARG(y == nullptr || (class_true && (target_width == 0 || bb_true)), "y needs class_true and bb_true");
+  const dim3 grid(rgnn_blocks(n, 256)), block(256);
+  if (y_is_f64)
+    hipLaunchKernelGGL(k_predict_rows<uint64_t>, grid, block, 0, (hipStream_t)stream, cls, ldc, n_classes, (const uint32_t*)bb, ldb,
+                       box_width, (const uint64_t*)y, ldy, target_width, n, prob, ldp, (uint32_t*)bb_out, ldo, (uint64_t*)class_true,
+                       (uint64_t*)bb_true, ldt);
+  else
+    hipLaunchKernelGGL(k_predict_rows<uint32_t>, grid, block, 0, (hipStream_t)stream, cls, ldc, n_classes, (const uint32_t*)bb, ldb,
+                       box_width, (const uint32_t*)y, ldy, target_width, n, prob, ldp, (uint32_t*)bb_out, ldo, (uint32_t*)class_true,
+                       (uint32_t*)bb_true, ldt);
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
 }

@@ -1376,6 +1376,68 @@ def softmax_rows(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def _out_rows(t: torch.Tensor, name: str, dtype, width: int, row0: int, n: int) -> int:
+    """Checks an output buffer of ``predict_rows`` ([R, width], rows contiguous, R >= row0 + n; written in place, so no copy
+    may stand in for it) and returns the address of its row ``row0``."""
+    _dev(t, name, dtype)
+    if t.dim() != 2 or t.shape[1] != width:
+        raise ValueError(f"`{name}` must be [rows, {width}], got {tuple(t.shape)}")
+    if (width > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < width):
+        raise ValueError(f"`{name}` is written in place: its rows must be contiguous")
+    if row0 + n > t.shape[0]:
+        raise ValueError(f"`{name}` has {t.shape[0]} rows, rows [{row0}, {row0 + n}) are to be written")
+    return t.data_ptr() + row0 * _ld(t) * t.element_size()
+
+
+def predict_rows(cls: torch.Tensor, bb: torch.Tensor, y: Optional[torch.Tensor], prob: torch.Tensor, bb_out: torch.Tensor,
+                 class_true: Optional[torch.Tensor] = None, bb_true: Optional[torch.Tensor] = None, row0: int = 0) -> None:
+    """The epilogue of a prediction step in one launch (rgnn_predict_rows), written into rows [row0, row0 + n) of whole-split
+    buffers: ``prob`` [R, K] f32 = softmax(``cls`` [n, K]) -- the bits of ``softmax_rows`` --, ``bb_out`` [R, W] f32 = ``bb``
+    [n, W], and, with ``y`` [n, 1 + Wy] (float32 or float64), ``class_true`` [R] = y[:, 0] and ``bb_true`` [R, Wy] = y[:, 1:]
+    in y's dtype, word for word.  Inputs may be row-strided views; ``y=None`` leaves the two target buffers alone."""
+    cls = _rowmajor(_dev(cls, "cls", torch.float32), "cls")
+    bb = _rowmajor(_dev(bb, "bb", torch.float32), "bb")
+    n, k = cls.shape
+    w = bb.shape[1]
+    if bb.shape[0] != n:
+        raise ValueError(f"`bb` has {bb.shape[0]} rows, `cls` has {n}")
+    if k < 1:
+        raise ValueError("`cls` needs at least one class column")
+    row0 = int(row0)
+    if row0 < 0:
+        raise ValueError("row0 must not be negative")
+    devs = {cls.device, bb.device}
+    p_prob = _out_rows(prob, "prob", torch.float32, k, row0, n)
+    p_bb = _out_rows(bb_out, "bb_out", torch.float32, w, row0, n)
+    devs |= {prob.device, bb_out.device}
+    p_y = p_ct = p_bt = None
+    ldy = ldt = wy = 0
+    f64 = False
+    if y is not None:
+        if class_true is None or bb_true is None:
+            raise ValueError("`y` needs `class_true` and `bb_true`")
+        if not isinstance(y, torch.Tensor) or y.dtype not in (torch.float32, torch.float64):
+            raise TypeError("radargnn_amd: `y` must be a float32 or float64 tensor")
+        y = _rowmajor(_dev(y, "y"), "y")
+        if y.shape[0] != n or y.shape[1] < 1:
+            raise ValueError(f"`y` must be [{n}, 1 + Wy], got {tuple(y.shape)}")
+        wy, f64 = y.shape[1] - 1, y.dtype == torch.float64
+        _dev(class_true, "class_true", y.dtype)
+        if class_true.dim() != 1 or (class_true.shape[0] > 1 and class_true.stride(0) != 1):
+            raise ValueError("`class_true` must be a contiguous vector")
+        if row0 + n > class_true.shape[0]:
+            raise ValueError(f"`class_true` has {class_true.shape[0]} rows, rows [{row0}, {row0 + n}) are to be written")
+        p_ct = class_true.data_ptr() + row0 * class_true.element_size()
+        p_bt = _out_rows(bb_true, "bb_true", y.dtype, wy, row0, n)
+        p_y, ldy, ldt = y.data_ptr(), _ld(y), _ld(bb_true)
+        devs |= {y.device, class_true.device, bb_true.device}
+    if len(devs) != 1:
+        raise RuntimeError(f"predict_rows: all tensors must live on one device, got {sorted(map(str, devs))}")
+    vp = lambda a: None if a is None else C.c_void_p(a)
+    check(lib.rgnn_predict_rows(_ptr(cls), _ld(cls), k, _ptr(bb), _ld(bb), w, vp(p_y), ldy, 1 if f64 else 0, wy, n,
+                                vp(p_prob), _ld(prob), vp(p_bb), _ld(bb_out), vp(p_ct), vp(p_bt), ldt, _stream()))
+
+
 # ------------------------------------------------------------------------------------------------ message passing
 def gather_rows(x: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
     x = _rowmajor(_dev(x, "x", torch.float32), "x")
