@@ -104,7 +104,7 @@ struct WinParams {
   int d; int n_ct;
   float* out; int ldo4; int o_bytes;
   float* out_absmax;
-  int abl;                             // experiments only (wrong results): 1 no row requests after the first tile, 2 no arithmetic, 4 no stores
+  int abl;                             // experiments only (wrong results): 1 no row requests after the first tile, 2 no arithmetic, 4 every store dropped (out of range)
 };
 
 __device__ __forceinline__ void wn_dma16(wn_i32x4 rsrc, int voff, int soff, unsigned lds_base) {
@@ -133,14 +133,18 @@ __global__ __launch_bounds__(256) void k_win_wplanes(const float* __restrict__ W
   t[96] = mt_u32x4{__float_as_uint((p_bias != nullptr && c < d) ? p_bias[c] : 0.f), 0u, 0u, 0u};
 }
 
-// Segments padded to 2 slots instead of 4 (r05, tests green): 13 % fewer slots on the r = 1 m graphs, and SLOWER
-// everywhere -- C2 152 -> 202 us per launch, k = 20: 265 -> 366 -- eight possible segment ends per tile are eight copies of the
-// straight-line end code per tile (the <true> instance spills), whatever the number of ends that occur.  4 it stays.
+// Segments padded to 2 slots instead of 4: 13 % fewer slots on the r = 1 m graphs, and SLOWER everywhere, with the r07 end path
+// as with r05's -- us per launch at 4 / at 2, same box, alternating: C2 D = 464 139 / 170, D = 272 77 / 99, k = 20 D = 464
+// 402 / 482 (r05: C2 152 / 202) -- eight possible segment ends per tile are eight end tests and eight copies of the straight-line
+// end code per tile, whatever the number of ends that occur.  4 it stays.
 constexpr int WN_PAD = 4;              // a target's slots are padded to a multiple of this (2 or 4): a GROUP of WN_PAD accumulator rows
 constexpr int WN_GPT = 16 / WN_PAD;    // groups per 16-slot tile of a stream (a segment can end at every group)
 constexpr int WN_GPS = 64 / WN_PAD;    // groups per stream
 constexpr int WN_TMAX = 512 / WN_PAD;  // targets a window can hold
 static_assert(WN_PAD == 2 || WN_PAD == 4, "segments are padded to 2 or 4 slots");
+// Store offset of a group that ends no segment: beyond every `out` the launch accepts (o_bytes < 2^31), with or without a lane's
+// channel part added, so the buffer's range check drops the store; target 0's offset 0 and the last row's stay clear of it.
+constexpr int WN_NOEND = (int)0x80000000u;
 constexpr int WN_UMAX = 176;           // distinct source rows of a window (plan guarantee): 22 KB per staged channel tile
 constexpr int WN_ROWBUF = WN_UMAX * 128;
 
@@ -208,12 +212,9 @@ __global__ __launch_bounds__(WN_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
     rp.z = __builtin_amdgcn_readfirstlane(p.plan_bytes);
     rp.w = 0x00020000;
   }
-  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, (short)0, p.o_bytes, 0x00020000);
   const int rA = lane & 31, hA = (rA >> 2) & 1, iA = ((rA >> 3) << 2) | (rA & 3);
   const int my_stream = 2 * wave + half;
   float amax = 0.f;
-  float ninf = -INFINITY;
-  asm volatile("" : "+v"(ninf));                             // (kept in a register: v_cndmask takes no literal)
 
   // descriptors of window w -> LDS (urow into half `up` of its table): one or two requests per wave, lanes beyond a table masked
   auto desc_dma = [&](const int w, const int up) {
@@ -267,20 +268,21 @@ __global__ __launch_bounds__(WN_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
     const int nU = misctab[0];
     const int nU8 = (nU + 7) >> 3;
     int nt = 0;
-    unsigned endbits = 0, anyend = 0, endA = 0, endB = 0;
+    unsigned anyend = 0;
     mt_u32x4 a1[4], a2[4], a3[4];
     int aoff[4][16];
-    int tv = 0;
+    int tv = WN_NOEND;
     if (nU != 0) {
-      // byte offsets (in `out`) of the target rows of this half's sixteen groups: lane j (and 32 + j) holds group j's -- where a
-      // segment ends the offset comes out of the register with v_readlane, not out of LDS
-      tv = tgttab[my_stream * WN_GPS + (lane & (WN_GPS - 1))] * p.ldo4;
       const uint8_t* m8 = (const uint8_t*)(misctab + 1);
       nt = max((int)m8[2 * wave], (int)m8[2 * wave + 1]);
       const uint8_t* e4 = m8 + 8 + my_stream * 4;
-      endbits = (unsigned)e4[0] | ((unsigned)e4[1] << WN_GPT) | ((unsigned)e4[2] << (2 * WN_GPT)) | ((unsigned)e4[3] << (3 * WN_GPT));
-      endA = (unsigned)__builtin_amdgcn_readlane((int)endbits, 0); endB = (unsigned)__builtin_amdgcn_readlane((int)endbits, 32);
-      anyend = endA | endB;
+      const unsigned endbits = (unsigned)e4[0] | ((unsigned)e4[1] << WN_GPT) | ((unsigned)e4[2] << (2 * WN_GPT)) | ((unsigned)e4[3] << (3 * WN_GPT));
+      anyend = (unsigned)__builtin_amdgcn_readlane((int)endbits, 0) | (unsigned)__builtin_amdgcn_readlane((int)endbits, 32);
+      // Lane j (and 32 + j) holds, for group j of its half's stream, the byte offset (in `out`) of the target row if the group ends
+      // a segment, and WN_NOEND if it does not: everything a segment end needs to know, once per window (the rows of tgttab of
+      // groups that end nothing are never looked at).
+      const int gj = lane & (WN_GPS - 1);
+      tv = ((endbits >> gj) & 1u) ? tgttab[my_stream * WN_GPS + gj] * p.ldo4 : WN_NOEND;
       // z of this wave's (up to) four tiles, split into its bf16 terms once for all channel tiles
 #pragma unroll
       for (int t = 0; t < 4; t++) {
@@ -346,13 +348,14 @@ __global__ __launch_bounds__(WN_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
       const mt_u32x4* bl = (const mt_u32x4*)(bstage + ST * WN_BBUF);
       const mt_u32x4 bxc = bl[(half ? 32 : 0) + col], byc = bl[(half ? 64 : 0) + col];
       const float biasc = __uint_as_float(bl[96 + col].x);
-      const int voffc = (ct * 32 + col < p.d) ? col4 : 0x7ffffff0;       // (out of range: the store is dropped)
-      const float ninf_l = ninf;
-      const __amdgpu_buffer_rsrc_t ro_l = ro;
+      const int voffc = (ct * 32 + col < p.d && !(p.abl & 4)) ? col4 : 0x7ffffff0;       // (out of range: the store is dropped)
+      // `out` as this channel tile sees it: base and size moved by the tile's 128 bytes, so no end adds them and the range check
+      // stays exact (ct * 32 < d: the size stays positive)
+      const __amdgpu_buffer_rsrc_t ro_l = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)p.out + ct * 128), (short)0, p.o_bytes - ct * 128, 0x00020000);
       float rn = -INFINITY;
-      // (what the segment ends derive from the end masks and the offset register is loop-invariant: without this hipcc hoists 64
-      //  scalars out of the channel-tile loop and spills them)
-      asm volatile("" : "+v"(tv), "+s"(endA), "+s"(endB), "+s"(anyend));
+      // (the end tests and the offsets read out of `tv` are loop-invariant: without this hipcc hoists them out of the channel-tile
+      //  loop, scalars per group and tile, and spills them)
+      asm volatile("" : "+v"(tv), "+s"(anyend));
 #pragma unroll
       for (int t = 0; t < 4; t++) {
         if (t < nt && !(p.abl & 2)) {
@@ -367,27 +370,23 @@ __global__ __launch_bounds__(WN_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
             rn = __builtin_fmaxf(__builtin_fmaxf(rn, c[WN_PAD * g]), c[WN_PAD * g + 1]);
             if (WN_PAD == 4) rn = __builtin_fmaxf(__builtin_fmaxf(rn, c[WN_PAD * g + 2]), c[WN_PAD * g + 3]);
             if ((anyend >> (WN_GPT * t + g)) & 1u) {
-              // A segment ends here in one half or in both.  Three vector instructions per end (bias, reset, maximum of |v|): the
-              // store offset is a SCALAR per half (v_readlane out of `tv` + the channel tile's offset) handed to the store as its
-              // soffset, one half-wave store per ending half under an exec mask set by hand; the reset is one v_cndmask under a
-              // lane mask assembled from the two end bits.  (r04: table read + lgkmcnt(0) per end and sixteen lane masks in SGPR
-              // pairs; a first r05 form with per-lane selects cost 14 vector instructions per end and lost 2.5 % on the r = 1 m
-              // batches, where three of four groups end a segment.)
-              const int k = WN_GPT * t + g;
+              // A segment ends here in one half or in both.  Two v_readlane give the two halves' entries of `tv` -- the target
+              // row's offset, or WN_NOEND in a half that does not end here -- and everything else follows from that one value per
+              // lane: a select by half, one add for the lane's channel, ONE store under the full exec mask (the buffer's range
+              // check drops the lanes of a half that does not end, and the columns beyond d), and the reset is a compare of the
+              // same register + v_cndmask.  No scalar arithmetic, no exec mask.  (r05/r06: scalar adds, bit tests and 64-bit
+              // selects for a hand-made exec mask and a reset mask on top of the two v_readlane, about 9 scalar and 8 vector
+              // instructions per end.  r07 first fetched the entry with ONE ds_bpermute_b32 per end, the group number as its
+              // immediate offset: 4 vector instructions per end, and SLOWER than this form on every graph -- C2 146 us against
+              // 139, k = 20 430 against 388, the parent 154 and 418 -- wherever the permutes were issued: the LDS pipe is what
+              // this kernel has least of.  r04: a table read + lgkmcnt(0) per end.)  Straight-line on purpose: every taken branch
+              // refills the instruction buffer, and on the r = 1 m batches three of four groups come through here.
               const float v = rn + biasc;
-              // (straight-line on purpose: every taken branch refills the instruction buffer, and on the r = 1 m batches three of
-              //  four groups come through here.  A half that does not end stores under an empty exec mask.)
-              const unsigned long long mA = ((endA >> k) & 1u) ? 0xffffffffull : 0ull, mB = ((endB >> k) & 1u) ? 0xffffffff00000000ull : 0ull;
-              const int soA = __builtin_amdgcn_readlane(tv, k) + ct * 128, soB = __builtin_amdgcn_readlane(tv, 32 + k) + ct * 128;
-              if (!(p.abl & 4)) {
-                // ONE store per ending group: the two halves' scalar offsets selected per lane, lanes of a half that does not end masked
-                const int off = (half ? soB : soA) + voffc;
-                asm volatile("s_mov_b64 exec, %3\n\tbuffer_store_dword %0, %1, %2, 0 offen nt\n\ts_mov_b64 exec, -1"
-                             : : "v"(v), "v"(off), "s"(ro_l), "s"(mA | mB) : "memory");
-              }
+              const int toA = __builtin_amdgcn_readlane(tv, WN_GPT * t + g), toB = __builtin_amdgcn_readlane(tv, 32 + WN_GPT * t + g);
+              const int tog = half ? toB : toA;
+              asm volatile("buffer_store_dword %0, %1, %2, 0 offen nt" : : "v"(v), "v"((unsigned)tog + (unsigned)voffc), "s"(ro_l) : "memory");
               if (AMAX) amax = fmaxf(amax, fabsf(v));           // (a half that does not end contributes a partial maximum: a bound all the same)
-              const unsigned long long m64 = mA | mB;
-              asm volatile("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(rn) : "v"(ninf_l), "s"(m64));
+              rn = (tog >= 0) ? -INFINITY : rn;                 // (every real offset is below 2^31, WN_NOEND is not)
             }
           }
         }
