@@ -20,11 +20,11 @@ import torch
 from torch import nn
 from torch.nn import ModuleList, ReLU, Sequential
 
-from .. import ops
+from .. import derived, ops
 from .configs import GNNArchitectureConfig
 from . import autograd as AG
 from .linear import BatchNorm, Linear, frame_scope, run_mlp
-from .mpnn_layers import DeferredEdgeAttr, MPNNConv, RadarPointGNNConv, TargetCSR, UnsortedEdgeAttr, _cache_key, _same_key, _state_without_caches
+from .mpnn_layers import DeferredEdgeAttr, MPNNConv, RadarPointGNNConv, TargetCSR, UnsortedEdgeAttr
 from . import linear as _lin_mod
 
 
@@ -124,7 +124,7 @@ class DetNetBasic(nn.Module):
     def __getstate__(self):
         # (whole-module pickles -- gnn/trainer.py:342-354, evaluate.py:46-52 -- and deepcopy carry parameters and buffers, not the
         #  weight-derived caches an inference pass leaves on the instance)
-        return _state_without_caches(self)
+        return derived.state_without_holder(self)
 
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_attr: torch.Tensor, frame_ptr: torch.Tensor = None):
         """-> (class logits [N, K], boxes [N, 4|5]); reference: gnn/gnn_models.py:104-134.
@@ -308,14 +308,7 @@ class DetNetBasic(nn.Module):
 
     def _negated(self, w: torch.Tensor) -> torch.Tensor:
         """-w, cached until w changes (one elementwise launch per weight version, outside captured steps)."""
-        key = (w.data_ptr(), w._version, ops.CACHE_EPOCH)
-        cache = self.__dict__.get("_neg_cache")
-        if cache is None or cache[0] != key:
-            # (kept in the instance dict, NOT through nn.Module.__setattr__: assigning the Parameter `w` as an attribute registered it
-            #  as a second parameter "_neg_keep" -- an extra key in state_dict() after the first inference pass, and a strict
-            #  load_state_dict of the original checkpoint failed)
-            cache = self.__dict__["_neg_cache"] = (key, (-w.detach()).contiguous(), w)
-        return cache[1]
+        return derived.get(self, "neg", (w,), lambda: (-w.detach()).contiguous())
 
     @staticmethod
     def _tiny_edge_hidden(hidden) -> bool:
@@ -343,15 +336,13 @@ class DetNetBasic(nn.Module):
         lins = (first[0], second[0])
         if any(l.bias is None for l in lins):
             return None
-        key = _cache_key((lins[0].weight, lins[0].bias, lins[1].weight, lins[1].bias))
         n0, n1 = lins[0].weight.shape[0], lins[1].weight.shape[0]
         pad = (-n0) % 4                  # zero columns between the heads: the second head's block starts 16-byte aligned
-        if not _same_key(getattr(self, "_heads_key", None), key):
+        def build():
             w0, b0 = lins[0].weight.detach(), lins[0].bias.detach()
-            self._heads_val = (torch.cat([w0, w0.new_zeros((pad, w0.shape[1])), lins[1].weight.detach()], 0).contiguous(),
-                               torch.cat([b0, b0.new_zeros(pad), lins[1].bias.detach()], 0).contiguous())
-            self._heads_key = key
-        w, b = self._heads_val
+            return (torch.cat([w0, w0.new_zeros((pad, w0.shape[1])), lins[1].weight.detach()], 0).contiguous(),
+                    torch.cat([b0, b0.new_zeros(pad), lins[1].bias.detach()], 0).contiguous())
+        w, b = derived.get(self, "heads", (lins[0].weight, lins[0].bias, lins[1].weight, lins[1].bias), build)
         relu_any = first[1] or second[1]
         out = ops.linear(h, w, b, relu=relu_any, relu_from=0 if first[1] else n0 + pad, a1_affine=scale_shift, a1_relu=True)
         res = [None, None]

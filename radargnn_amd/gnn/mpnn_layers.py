@@ -28,7 +28,7 @@ import torch
 from torch import nn
 from torch.nn import ReLU, Sequential
 
-from .. import ops
+from .. import derived, ops
 from . import autograd as AG
 from .linear import Linear, run_mlp
 
@@ -342,26 +342,6 @@ class TargetCSR:
         return self.split_targets()[:3]
 
 
-def _cache_key(tensors):
-    """Identity of a set of weight tensors for the folded-weight caches: the tensors themselves (kept alive by the key, so
-    their storage -- and with it the address -- cannot be recycled by a replacement Parameter), their version counters, the
-    global epoch, and where their data lives right now: ``module.to(device)`` / ``.float()`` swap ``param.data`` under the
-    SAME Parameter object without touching its version counter."""
-    return (ops.CACHE_EPOCH, tuple(tensors), tuple(t._version for t in tensors),
-            tuple((t.data_ptr(), t.device, t.dtype) for t in tensors))
-
-
-def _same_tensor(x: torch.Tensor, y: torch.Tensor) -> bool:
-    # `.detach()` hands out a new Python object over the same memory on every call (DetNetBasic passes the edge-embedding
-    # tail that way), so identity is storage address + geometry, not `is`
-    return x is y or (x.data_ptr() == y.data_ptr() and x.shape == y.shape and x.stride() == y.stride() and x.dtype == y.dtype)
-
-
-def _same_key(a, b) -> bool:
-    return (a is not None and a[0] == b[0] and len(a[1]) == len(b[1]) and all(_same_tensor(x, y) for x, y in zip(a[1], b[1]))
-            and a[2] == b[2] and a[3] == b[3])
-
-
 def _message_mlp(dim: int, layers: int) -> Sequential:
     mods = [Linear(dim, dim)]
     for _ in range(layers - 1):
@@ -388,21 +368,13 @@ def _fold_edge_tail(We: torch.Tensor, p_bias: Optional[torch.Tensor], edge_tail)
     return ops.linear(We, tw.t().contiguous()), p_bias          # W_e W  [D, Dz]
 
 
-# per-instance caches of weight-derived tensors (folded weights, summed biases): recomputed on first use, keyed on parameter identity
-# and version -- never part of a pickle (torch.save(model) / copy.deepcopy(model), gnn/trainer.py:128-130,342-354) or of a state_dict
-_CACHE_ATTRS = ("_fold_val", "_fold_key", "_edge_fold_val", "_edge_fold_key", "_tail_val", "_tail_key", "_sum_bias_val", "_sum_bias_key",
-                "_sum_bias_keep", "_neg_cache", "_heads_val", "_heads_key")
-
-
-def _state_without_caches(module: nn.Module) -> dict:
-    return {k: v for k, v in module.__dict__.items() if k not in _CACHE_ATTRS}
-
-
 class _ConvBase(nn.Module):
     aggr: str
 
     def __getstate__(self):
-        return _state_without_caches(self)
+        # (folded weights and summed biases live in ONE holder attribute, derived.py: never part of a pickle -- torch.save(model) /
+        #  copy.deepcopy(model), gnn/trainer.py:128-130,342-354 -- or of a state_dict)
+        return derived.state_without_holder(self)
 
     def reset_parameters(self):
         if getattr(self, "use_edge_encoder", False):
@@ -635,8 +607,7 @@ class MPNNConv(_ConvBase):
         (M' = aggregated source/edge part, exactly 0 for isolated targets).  Returns the combined weight
         [W_px + W_pm W_i | W_pm] and the combined bias.  Cached until a parameter is modified in place / replaced."""
         pre, post = self.pre_mlp[0], self.post_mlp[0]
-        key = _cache_key((pre.weight, pre.bias, post.weight, post.bias))
-        if not _same_key(getattr(self, "_fold_key", None), key):
+        def build():
             c = self.in_channels
             W, b = pre.weight.detach(), pre.bias.detach()
             Wp, bp = post.weight.detach(), post.bias.detach()
@@ -644,9 +615,8 @@ class MPNNConv(_ConvBase):
             Wpx, Wpm = Wp[:, :c], Wp[:, c:]
             wfold = ops.linear(Wpm, Wi.t().contiguous())                 # W_pm W_i   [Co, C]
             bfold = ops.linear(Wpm, b.view(1, -1)).view(-1)              # W_pm b     [Co]
-            self._fold_val = (torch.cat([Wpx + wfold, Wpm], dim=1).contiguous(), (bp + bfold).contiguous())
-            self._fold_key = key
-        return self._fold_val
+            return torch.cat([Wpx + wfold, Wpm], dim=1).contiguous(), (bp + bfold).contiguous()
+        return derived.get(self, "fold", (pre.weight, pre.bias, post.weight, post.bias), build)
 
     def _folded_edge_weights(self, edge_tail):
         """(W_e with the edge encoder / the edge-embedding tail folded in, its bias term) -- [D, De']-sized products of
@@ -655,18 +625,16 @@ class MPNNConv(_ConvBase):
         if self.use_edge_encoder:
             tensors += [self.edge_encoder.weight, self.edge_encoder.bias]
         if edge_tail is not None:
-            tensors += [t for t in edge_tail if t is not None]
-        key = _cache_key(tensors)
-        if not _same_key(getattr(self, "_edge_fold_key", None), key):
+            tensors += edge_tail
+        def build():
             c = self.in_channels
             We, p_bias = self.pre_mlp[0].weight.detach()[:, 2 * c:], None
             if self.use_edge_encoder:
                 enc_w, enc_b = self.edge_encoder.weight.detach(), self.edge_encoder.bias.detach()
                 p_bias = ops.linear(We, enc_b.view(1, -1)).view(-1)
                 We = ops.linear(We, enc_w.t().contiguous())
-            self._edge_fold_val = _fold_edge_tail(We, p_bias, edge_tail)
-            self._edge_fold_key = key
-        return self._edge_fold_val
+            return _fold_edge_tail(We, p_bias, edge_tail)
+        return derived.get(self, "edge_fold", tensors, build)
 
     def _input_tail_weights(self, x_tail, edge_tail):
         """The layer's weights with a Linear in front of it folded in: the layer input is x = t W_t^T + b_t (the last Linear of
@@ -682,9 +650,8 @@ class MPNNConv(_ConvBase):
         like the other folds; cached per weight version."""
         tw, tb = x_tail
         pre, post = self.pre_mlp[0], self.post_mlp[0]
-        tensors = [pre.weight, pre.bias, post.weight, post.bias, tw] + ([tb] if tb is not None else [])
-        key = _cache_key(tensors)
-        if not _same_key(getattr(self, "_tail_key", None), key):
+        tensors = (pre.weight, pre.bias, post.weight, post.bias, tw, tb)
+        def build():
             c = self.in_channels
             wcomb, bcomb = self._folded_update_weights()
             Wj = pre.weight.detach()[:, c:2 * c]
@@ -701,9 +668,8 @@ class MPNNConv(_ConvBase):
                 biso_t = (post.bias.detach() + ops.linear(Wpx.contiguous(), b).view(-1)).contiguous()
             else:
                 qb, bcomb_t, biso_t = None, bcomb, post.bias.detach()
-            self._tail_val = (wj_t.contiguous(), qb, wcomb_t, bcomb_t, wpx_t.contiguous(), biso_t)
-            self._tail_key = key
-        return self._tail_val
+            return wj_t.contiguous(), qb, wcomb_t, bcomb_t, wpx_t.contiguous(), biso_t
+        return derived.get(self, "tail", tensors, build)
 
     def _forward_folded(self, x, graph, ea_sorted, want_stats, edge_tail, x_affine=None, x_tail=None, frames=None):
         c = self.in_channels
@@ -770,10 +736,7 @@ class MPNNConv(_ConvBase):
 
     def _sum_bias(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
         """a + b for two [D] bias vectors, cached on their identities (one elementwise launch per weight version, not per step)."""
-        key = (a.data_ptr(), a._version, b.data_ptr(), b._version)
-        if getattr(self, "_sum_bias_key", None) != key:
-            self._sum_bias_val, self._sum_bias_key, self._sum_bias_keep = (a + b).contiguous(), key, (a, b)
-        return self._sum_bias_val
+        return derived.get(self, "sum_bias", (a, b), lambda: (a + b).contiguous())
 
     def message(self, x_i: torch.Tensor, x_j: torch.Tensor, edge_attr: torch.Tensor) -> torch.Tensor:
         """Per-edge message exactly as the reference spells it (mpnn_layers.py:94-101); not used by forward."""

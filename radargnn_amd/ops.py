@@ -6,11 +6,12 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import sys
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, derived
 from ._lib import RgnnError, RgnnGrid, RgnnLinearArgs, check, lib
 
 EDGE_FEATURE_CODES = {
@@ -36,8 +37,8 @@ class ForwardContext:
       profiler     optional launch profiler (bench.py): an object with ``.begin(kind)`` -> token and ``.end(token, **work)``;
                    ``begin`` arms a pair of HIP events through rgnn_profile_next_launch(), which the library records immediately
                    around the kernel launch (no Python between the event and the launch).  None = no overhead.
-    Process-wide state that remains: the weight-plane caches (keyed on the weights; entries carry the event of the stream that
-    filled them), the split-K scratch (one per device and stream), COUNTERS (diagnostics for the tests)."""
+    Process-wide state that remains: the weight-derived cache's two plane tables and its epoch (derived.py: keyed on the weights; every
+    entry carries the event of the stream that filled it), the split-K scratch (one per device and stream), COUNTERS (diagnostics)."""
     __slots__ = ("bounds", "frame_scope", "profiler", "_side", "_finalizer", "__weakref__")
 
     def __init__(self):
@@ -206,8 +207,7 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-_raw_device = getattr(torch._C, "_cuda_getDevice", None)
+_raw_stream, _raw_device = derived._raw_stream, derived._raw_device
 
 
 def _stream_id(device=None) -> int:
@@ -663,8 +663,9 @@ COUNTERS = {"fused_a1_affine": 0}          # launches per kind since import (tes
 FUSE_A1_AFFINE = __import__("os").environ.get("RGNN_NO_FUSED_BN_APPLY") is None   # BatchNorm-apply inside the consumer GEMM's A path
 USE_MAX_BWD = __import__("os").environ.get("RGNN_MPNN_BWD_OLD") is None     # max aggregation backward: rgnn_mpnn_max_bwd where it applies
 BF16X3_MIN_COLS = int(__import__('os').environ.get('RGNN_X3_MIN_COLS', '32'))
-_PLANES = {}
-CACHE_EPOCH = 0          # part of every weight-derived cache key (planes here, folded weights in gnn/mpnn_layers.py)
+CACHE_EPOCH = 0          # part of every weight-derived cache key: derived.py reads it here at each lookup
+derived.epoch_owner = sys.modules[__name__]
+_PLANES, _PLANES16 = derived.Table(), derived.Table()      # bf16 / f16 weight planes (weight_planes, weight_planes_f16)
 
 
 _SPLITK_WS = {}
@@ -696,7 +697,6 @@ CHECK_BOUNDS = __import__("os").environ.get("RGNN_CHECK_BOUNDS") is not None
 WGRAD_F16X2 = __import__("os").environ.get("RGNN_NO_WGRAD_F16X2") is None       # weight gradients in the f16x2 form inside a bound pool
 BN_BWD_MASK_FROM_TABLE = __import__("os").environ.get("RGNN_BN_BWD_READS_Y") is None   # BatchNorm backward: ReLU mask from h + apply table
 TRAIN_F16X2 = __import__("os").environ.get("RGNN_NO_TRAIN_F16X2") is None      # recorded (training) forwards and their backward track bounds too
-_PLANES16 = {}
 
 
 BOUND_SLOTS = 256        # rgnn.h RGNN_BOUND_SLOTS: a bound is 256 float words, producers raise one slot per work-group
@@ -834,81 +834,20 @@ def invalidate_weight_caches() -> None:
     CACHE_EPOCH += 1
     _PLANES.clear()
     _PLANES16.clear()
-    _LATEST.clear()
-    _LATEST16.clear()
-
-
-_LATEST, _LATEST16 = {}, {}      # (weight views without their version) -> key of the newest cache entry made for them
-
-
-def _replace_older(latest: dict, cache: dict, key) -> None:
-    """A new entry for the same weight views supersedes the one made for an older version (an optimizer step bumps the version of
-    every parameter: without this a training loop parks 18 dead plane sets per step until the 128-entry sweep)."""
-    gkey = tuple(None if k is None else (k[0],) + k[2:] for k in key[:2])
-    old = latest.get(gkey)
-    if old is not None and old != key:
-        cache.pop(old, None)
-    latest[gkey] = key
-
-
-def _wkey(w: Optional[torch.Tensor]):
-    if w is None:
-        return None, None
-    st = w.untyped_storage()
-    return st, (st._cdata, w._version, w.storage_offset(), tuple(w.shape), w.stride())
-
-
-def _filled_on_this_stream():
-    """(event, stream id) recorded behind the launch that just filled a cache entry: a later hit from ANOTHER stream waits for the
-    event first (the same model driven on two streams; entries made inside a stream capture carry none -- a capture's own
-    launches are ordered by the graph)."""
-    st = torch.cuda.current_stream()
-    if torch.cuda.is_current_stream_capturing():
-        return None, st.cuda_stream
-    ev = torch.cuda.Event()
-    ev.record(st)
-    return ev, st.cuda_stream
-
-
-def _order_behind(ev, stream_id, planes: Optional[torch.Tensor] = None) -> None:
-    """A cache hit from a stream other than the one that filled the entry: wait for the fill, and tell the caching allocator that
-    THIS stream reads the planes too -- an entry evicted (replaced by a newer weight version, the 128-entry sweep,
-    invalidate_weight_caches) while a launch of this stream still reads it must not have its block handed out again before that
-    launch is through (the allocator only orders reuse on the allocating stream)."""
-    if _stream_id() == stream_id:                     # (the common case, ~40 cache hits per step: no stream object is built)
-        return
-    st = torch.cuda.current_stream()
-    if st.cuda_stream != stream_id:
-        if ev is not None:
-            st.wait_event(ev)
-        if planes is not None and not torch.cuda.is_current_stream_capturing():
-            planes.record_stream(st)
 
 
 def weight_planes(w1: torch.Tensor, w2: Optional[torch.Tensor], k: int, cache: bool = True):
-    """Three bf16 planes of [w1; w2] (rgnn_linear_split_weights), cached per weight storage, version (in-place updates
-    bump it, also through detached aliases and views) and view geometry.  The entry keeps the storage alive, so its
-    address cannot be recycled for another tensor while the entry exists; the cache is dropped when it reaches 128
-    entries (temporaries such as the transposed weights of the backward pass)."""
-    s1, k1_ = _wkey(w1)
-    s2, k2_ = _wkey(w2)
-    key = (k1_, k2_, CACHE_EPOCH)
-    hit = _PLANES.get(key) if cache else None
-    if hit is not None:
-        _order_behind(hit[4], hit[5], hit[0])
-        return hit[0], hit[1]
-    if cache and len(_PLANES) >= 128:
-        _PLANES.clear()
-        _LATEST.clear()
-    n1 = w1.shape[0]
-    n = n1 + (0 if w2 is None else w2.shape[0])
-    kp = int(lib.rgnn_linear_planes_kp(k))
-    planes = torch.empty((3, n, kp), dtype=torch.bfloat16, device=w1.device)
-    check(lib.rgnn_linear_split_weights(_ptr(w1), _ptr(w2), _ld(w1), n1, n, k, _ptr(planes), _stream()))
-    if cache:
-        _replace_older(_LATEST, _PLANES, key)
-        _PLANES[key] = (planes, kp, s1, s2, *_filled_on_this_stream())
-    return planes, kp
+    """(three bf16 planes of [w1; w2], their row length) (rgnn_linear_split_weights), cached per memory, view geometry and version of
+    the two weights (derived.py: in-place updates bump the version, also through detached aliases and views); ``cache=False``:
+    built for this launch only (temporaries such as the transposed weights of the backward pass)."""
+    def build():
+        n1 = w1.shape[0]
+        n = n1 + (0 if w2 is None else w2.shape[0])
+        kp = int(lib.rgnn_linear_planes_kp(k))
+        planes = torch.empty((3, n, kp), dtype=torch.bfloat16, device=w1.device)
+        check(lib.rgnn_linear_split_weights(_ptr(w1), _ptr(w2), _ld(w1), n1, n, k, _ptr(planes), _stream()))
+        return planes, kp
+    return derived.get(_PLANES, "x3", (w1, w2), build) if cache else build()
 
 
 PAD_ROWS = __import__("os").environ.get("RGNN_NO_PADDED_ROWS") is None
@@ -927,24 +866,13 @@ def padded_rows(m: int, n: int, device) -> torch.Tensor:
 
 def weight_planes_f16(w1: torch.Tensor, w2: Optional[torch.Tensor], k: int, cache: bool = True) -> torch.Tensor:
     """The two f16 planes of [w1; w2] * 2^sw plus their footer (rgnn_linear_split_weights_f16), cached like ``weight_planes``."""
-    s1, k1_ = _wkey(w1)
-    s2, k2_ = _wkey(w2)
-    key = (k1_, k2_, CACHE_EPOCH)
-    hit = _PLANES16.get(key) if cache else None
-    if hit is not None:
-        _order_behind(hit[3], hit[4], hit[0])
-        return hit[0]
-    if cache and len(_PLANES16) >= 128:
-        _PLANES16.clear()
-        _LATEST16.clear()
-    n1 = w1.shape[0]
-    n = n1 + (0 if w2 is None else w2.shape[0])
-    planes = torch.empty(int(lib.rgnn_linear_planes_f16_bytes(n, k)), dtype=torch.uint8, device=w1.device)
-    check(lib.rgnn_linear_split_weights_f16(_ptr(w1), _ptr(w2), _ld(w1), n1, n, k, _ptr(planes), _stream()))
-    if cache:
-        _replace_older(_LATEST16, _PLANES16, key)
-        _PLANES16[key] = (planes, s1, s2, *_filled_on_this_stream())
-    return planes
+    def build():
+        n1 = w1.shape[0]
+        n = n1 + (0 if w2 is None else w2.shape[0])
+        planes = torch.empty(int(lib.rgnn_linear_planes_f16_bytes(n, k)), dtype=torch.uint8, device=w1.device)
+        check(lib.rgnn_linear_split_weights_f16(_ptr(w1), _ptr(w2), _ld(w1), n1, n, k, _ptr(planes), _stream()))
+        return planes
+    return derived.get(_PLANES16, "f16", (w1, w2), build) if cache else build()
 
 
 def linear(a1: torch.Tensor, w1: torch.Tensor, bias1: Optional[torch.Tensor] = None, *, a2: Optional[torch.Tensor] = None,
@@ -1520,18 +1448,11 @@ def _win_operand_image(We: Optional[torch.Tensor], p_bias: Optional[torch.Tensor
     would belong to that graph's pool) -- the launch then builds its own image in the plan's scratch."""
     if We is None or de == 0 or de > 8 or not WIN_IMAGE_CACHE:        # (de > 8: the launch itself refuses, RGNN_ERR_UNSUPPORTED)
         return None
-    hit = getattr(We, "_rgnn_wplanes", None)
-    if (hit is not None and hit[1] == We._version and hit[2] is p_bias and (p_bias is None or hit[3] == p_bias._version)
-            and hit[4] == CACHE_EPOCH):
-        _order_behind(hit[5], hit[6], hit[0])
-        return hit[0]
-    if torch.cuda.is_current_stream_capturing():
-        return None
-    planes = torch.empty(int(lib.rgnn_mpnn_win_wplanes_bytes(d)), dtype=torch.uint8, device=We.device)
-    check(lib.rgnn_mpnn_win_wplanes(_ptr(We), _ld(We), de, d, _ptr(p_bias), _ptr(planes), _stream()))
-    ev, sid = _filled_on_this_stream()
-    We._rgnn_wplanes = (planes, We._version, p_bias, None if p_bias is None else p_bias._version, CACHE_EPOCH, ev, sid)
-    return planes
+    def build():
+        planes = torch.empty(int(lib.rgnn_mpnn_win_wplanes_bytes(d)), dtype=torch.uint8, device=We.device)
+        check(lib.rgnn_mpnn_win_wplanes(_ptr(We), _ld(We), de, d, _ptr(p_bias), _ptr(planes), _stream()))
+        return planes
+    return derived.get(We, "win_image", (We, p_bias), build, build_in_capture=False)
 
 
 def mpnn_aggregate_win(p_bias, Q, We, ea_sorted, rowptr_t, src_sorted, plan: torch.Tensor,

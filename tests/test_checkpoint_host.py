@@ -17,7 +17,7 @@ import pytest
 import torch
 from torch import nn
 
-from radargnn_amd import checkpoint, gnn
+from radargnn_amd import checkpoint, derived, gnn
 
 
 # ---- the stand-in "reference environment" ------------------------------------------------------------------------------------------
@@ -239,15 +239,17 @@ def test_whole_module_pickle_of_the_hip_model_carries_no_caches():
     instances (folded weights, negated / concatenated weights) stay out of both."""
     cfg = CFGS[0]
     model = gnn.DetNetBasic(cfg)
-    model.__dict__["_neg_cache"] = ("key", torch.zeros(3), None)
-    model._heads_val, model._heads_key = (torch.zeros(2), torch.zeros(2)), "k"
-    model.convs[0]._fold_val, model.convs[0]._fold_key = (torch.zeros(4), torch.zeros(4)), "k"
+    conv = model.convs[0]
+    derived.get(model, "neg", (conv.pre_mlp[0].weight,), lambda: torch.zeros(3))
+    derived.get(model, "heads", (conv.pre_mlp[0].weight, conv.pre_mlp[0].bias), lambda: (torch.zeros(2), torch.zeros(2)))
+    derived.get(conv, "fold", (conv.pre_mlp[0].weight,), lambda: (torch.zeros(4), torch.zeros(4)))
+    assert set(model.__dict__[derived.HOLDER]) == {"neg", "heads"} and set(conv.__dict__[derived.HOLDER]) == {"fold"}
     buf = io.BytesIO()
     torch.save(model, buf)
     buf.seek(0)
     back = torch.load(buf, weights_only=False)
     for m in (back, copy.deepcopy(model)):
-        assert "_neg_cache" not in m.__dict__ and not hasattr(m, "_heads_val") and not hasattr(m.convs[0], "_fold_val")
+        assert derived.HOLDER not in m.__dict__ and not hasattr(m, derived.HOLDER) and not hasattr(m.convs[0], derived.HOLDER)
         assert all(torch.equal(a, b) for a, b in zip(m.state_dict().values(), model.state_dict().values()))
     assert set(back.state_dict()) == set(model.state_dict())
 

@@ -186,16 +186,16 @@ def test_shard_range_is_a_partition():
 def test_fold_cache_key_sees_swapped_parameter_storage():
     """nn.Module._apply (.to(device), .float()) replaces ``param.data`` under the same Parameter object and version counter;
     the folded-weight cache key has to change with it."""
-    from radargnn_amd.gnn import mpnn_layers as ml
+    from radargnn_amd import derived
     p = torch.nn.Parameter(torch.ones(4, 4))
-    k0 = ml._cache_key((p,))
-    assert ml._same_key(k0, ml._cache_key((p,)))
+    k0 = derived.key_of("fold", (p,))
+    assert k0 == derived.key_of("fold", (p,))
     p.data = p.data.clone()
-    assert not ml._same_key(k0, ml._cache_key((p,)))
-    k1 = ml._cache_key((p,))
+    assert k0 != derived.key_of("fold", (p,))
+    k1 = derived.key_of("fold", (p,))
     with torch.no_grad():
         p.add_(1.0)
-    assert not ml._same_key(k1, ml._cache_key((p,)))
+    assert k1 != derived.key_of("fold", (p,))
 
 
 def test_bench_decides_when_to_launch_its_own_ranks():
