@@ -526,6 +526,13 @@ int rgnn_scale_shift_act(const float* x, int64_t ldx, const float* scale_shift, 
  * P (may be NULL: RadarPointGNNConv has no x_i term, only `p_bias`) and Q are node-wise projections
  * produced by rgnn_linear_fwd.  Edges are visited in CSR-by-target order; `edge_attr_sorted` is
  * edge_attr[perm].  aggr: 0 = max, 1 = mean, 2 = add; empty segments give exactly 0 (torch-scatter).
+ * aggr 3 = min, 4 = var, 5 = std (torch_geometric 2.1 nn/aggr/basic.py), per channel over the messages m_e of a segment of cnt edges:
+ *   min: P + b + min_e(Q[s_e] + W_e a_e) on targets with edges, exactly 0 on the others;
+ *   var: mean_e(m_e^2) - (mean_e m_e)^2, not clamped, 0 on empty segments;   std: sqrt(relu(var) + 1e-5), sqrt(1e-5) on empty segments.
+ *   var and std do not change when every message of a segment is shifted by the same amount: P AND p_bias ARE IGNORED for codes 4
+ *   and 5 (never read; pass NULL).  The sums run over d_e = m_e - m_0 (m_0: the segment's first message in CSR order), var =
+ *   sum d^2 / cnt - (sum d / cnt)^2: a segment of one edge or of equal messages gives exactly 0 (std: exactly sqrtf(1e-5f)).
+ *   These codes write every row (RGNN_MPNN_SKIP_EMPTY_ROWS is accepted and has no effect) and track out_absmax in the kernel.
  * `node_order` (with a CSR built with the matching `target_rank`) only changes the order in which targets are
  * processed (cache locality), never the result: segment p of the CSR belongs to target node_order[p].
  * Replaces MessagePassing.propagate (index_select gathers + cat + addmm + scatter) at
@@ -538,6 +545,9 @@ int rgnn_scale_shift_act(const float* x, int64_t ldx, const float* scale_shift, 
 #define RGNN_AGGR_MAX 0
 #define RGNN_AGGR_MEAN 1
 #define RGNN_AGGR_ADD 2
+#define RGNN_AGGR_MIN 3
+#define RGNN_AGGR_VAR 4
+#define RGNN_AGGR_STD 5
 #define RGNN_MPNN_SKIP_EMPTY_ROWS 1
 int rgnn_mpnn_aggregate(const float* P, int64_t ldp, const float* p_bias, const float* Q, int64_t ldq,
                         const float* We /*[d, de], row stride ldwe*/, int64_t ldwe, const float* edge_attr_sorted,
@@ -628,7 +638,8 @@ int32_t rgnn_mpnn_target_weight(int64_t n, int64_t n_edges);
 int rgnn_mpnn_partition(const int32_t* rowptr_t, int64_t n, int64_t n_edges, int32_t* chunk_start, rgnn_stream_t stream);
 
 /* General path (pre_layers > 1): first message layer per edge, hidden[e,:] = relu?(P[t_e] + Q[s_e] + W_e a_e),
- * rows in CSR-by-target order, then rgnn_linear_fwd on the [E,d] rows, then rgnn_segment_reduce. */
+ * rows in CSR-by-target order, then rgnn_linear_fwd on the [E,d] rows, then rgnn_segment_reduce (aggr 0 .. 5 as above, literally over
+ * the rows of a segment: nothing is hoisted or ignored here). */
 int rgnn_mpnn_edge_hidden(const float* P, int64_t ldp, const float* p_bias, const float* Q, int64_t ldq,
                           const float* We, int64_t ldwe, const float* edge_attr_sorted, int32_t de,
                           const int32_t* rowptr_t, const int32_t* src_sorted, const int32_t* node_order,
@@ -834,7 +845,8 @@ int rgnn_bn_bwd_coef(const float* fwd_stats, int64_t panels_f, const float* runn
                      int32_t use_batch, float* coef, float* dgamma, float* dbeta, rgnn_stream_t stream);
 
 /* Backward of rgnn_segment_reduce: d_rows [E, d] (every row is written; rows of the forward input are needed for the
- * arg-max: the first row of a segment attaining the maximum receives dM[t, c]; mean / add: every row, / deg). */
+ * arg-max: the first row of a segment attaining the maximum receives dM[t, c]; mean / add: every row, / deg; min: the first row
+ * attaining the minimum; var: dM 2 (row - mean) / cnt; std: dM (row - mean) / (cnt std) where var > 0, else 0). */
 int rgnn_segment_reduce_bwd(const float* dM, int64_t lddm, const float* rows, int64_t ldr, const int32_t* rowptr_t,
                             const int32_t* node_order, int64_t n, int32_t d, int32_t aggr, float* d_rows, int64_t lddr,
                             rgnn_stream_t stream);
@@ -890,7 +902,12 @@ int rgnn_wgrad(const float* G, int64_t ldg, int32_t n, const float* A1, int64_t 
  *                 tnode[j] = target of out-edge j, tpos[j] = position of that edge in the target-sorted list):
  *                 dQ [n, d] is written for every node.
  * target_scale: float [n], 1 / in-degree (mean only, else NULL).  dwe_partial: float [rgnn_mpnn_bwd_slots(n), d, de]
- * workspace (every persistent wave group stores its share of dW_e, a last kernel sums them into dWe: no atomics). */
+ * workspace (every persistent wave group stores its share of dW_e, a last kernel sums them into dWe: no atomics).
+ * min (3): as max with the comparison turned round (arg_tmp int32 [n, d]: the first edge attaining the minimum).
+ * var (4) / std (5): every edge receives g_e = A[t] (m_e - mean[t]), A = dM 2 / cnt (var) or dM 1[var > 0] / (cnt std) (std), m_e
+ * recomputed from Q[s_e] + W_e a_e; d_edge_attr_e = W_e^T g_e, dWe = sum g_e a_e^T, dQ[s] = sum over the out-edges of s of g_e in
+ * fixed order.  For these two codes arg_tmp is a FLOAT workspace of 2 n d words (16-byte aligned for the vector form): a pre-pass
+ * writes A into its first half and mean into its second; target_scale is not read. */
 int64_t rgnn_mpnn_bwd_slots(int64_t n);
 /* waves per segment of the edge half (1, 2 or 4); dea_partial: float [split, E, de] workspace when split > 1 */
 int32_t rgnn_mpnn_bwd_split(int32_t d);

@@ -175,13 +175,14 @@ __device__ __forceinline__ float4 load4(const float* __restrict__ row, int cb, i
 //   k_mpnn_bwd_edge routes dM[t, c] to that edge (mean / add: to every edge, / deg): d_edge_attr (atomic when CS > 1:
 //                   every wave adds its channels' share) and the per-slot partial of dW_e.
 // The node half (k_mpnn_bwd_src) turns arg into dQ without atomics.
-template <int CS, int DEP, bool VEC, bool LOC = false>
+template <int CS, int DEP, bool VEC, bool LOC = false, bool MIN = false>
 __global__ __launch_bounds__(256) void k_mpnn_bwd_arg(const float* __restrict__ Q, int64_t ldq, const float* __restrict__ We,
                                                      int64_t ldwe, const float* __restrict__ ea, int de,
                                                      const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src,
                                                      const int32_t* __restrict__ node_order, int64_t n, int d,
                                                      int32_t* __restrict__ arg_out) {
   // LOC: arg_out is a uint16 [n, d] array of indices INSIDE the segment (rgnn_mpnn_max_bwd); else int32 edge positions
+  // MIN: the comparison turned round (min aggregation: the first edge that attains the MINIMUM)
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int64_t n_slots = (int64_t)gridDim.x * (blockDim.x >> 6) / CS;
@@ -197,7 +198,8 @@ __global__ __launch_bounds__(256) void k_mpnn_bwd_arg(const float* __restrict__ 
     const int r0 = rowptr[p], r1 = rowptr[p + 1];
     if (r1 == r0) continue;
     const int64_t t = node_order ? (int64_t)node_order[p] : p;
-    float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    const float worst = MIN ? INFINITY : -INFINITY;
+    float4 best = make_float4(worst, worst, worst, worst);
     int arg[4] = {-1, -1, -1, -1};
     // gathers two edges ahead of the compare (the row address depends on a loaded index)
     float4 q0 = load4<VEC>(Q + (int64_t)src[r0] * ldq, cb, d);
@@ -219,10 +221,10 @@ __global__ __launch_bounds__(256) void k_mpnn_bwd_arg(const float* __restrict__ 
           v[k] += a;
         }
       }
-      if (v[0] > best.x) { best.x = v[0]; arg[0] = e; }
-      if (v[1] > best.y) { best.y = v[1]; arg[1] = e; }
-      if (v[2] > best.z) { best.z = v[2]; arg[2] = e; }
-      if (v[3] > best.w) { best.w = v[3]; arg[3] = e; }
+      if (MIN ? v[0] < best.x : v[0] > best.x) { best.x = v[0]; arg[0] = e; }
+      if (MIN ? v[1] < best.y : v[1] > best.y) { best.y = v[1]; arg[1] = e; }
+      if (MIN ? v[2] < best.z : v[2] > best.z) { best.z = v[2]; arg[2] = e; }
+      if (MIN ? v[3] < best.w : v[3] > best.w) { best.w = v[3]; arg[3] = e; }
     }
     if (LOC) {
       uint2 pk;
@@ -678,6 +680,265 @@ __global__ __launch_bounds__(256) void k_mpnn_bwd_src_max16(const float* __restr
   }
 }
 
+// ---- var / std aggregation: every edge of a segment receives  g_e = A[t] (m_e - mean[t])  per channel, with
+//        var : A = dM 2 / cnt            std : A = dM 1[var > 0] / (cnt std)            m_e = Q[s_e] + W_e a_e (recomputed)
+// (the closed forms of d var / d m_e and d std / d m_e; the subtraction is done before the product, so a common offset of a
+// segment's messages costs no digits).  Three kernels, the work decomposition of the max machinery above:
+//   k_mpnn_bwd_coef      pre-pass over the CSR by target: repeats the forward's gather (twice: shifted sums, then centred ones)
+//                        and writes A and mean per (t, c) into coef float [2, n, d] (the arg workspace);
+//   k_mpnn_bwd_edge_var  d_edge_attr_e = W_e^T g_e and the per-slot partials of dW_e = sum g_e a_e^T;
+//   k_mpnn_bwd_src_var   dQ[s] = sum over the out-edges of s of g_e, a gather over the CSR by source in fixed order, no atomics.
+// The message arithmetic (a = sum_j w_j z_j in ascending j, then q + a) is the same in all three, so `m_e - mean` sees the m_e
+// the mean was made from.
+template <int DEP>
+__device__ __forceinline__ void bwd_message(const float4 qv, const float (&w)[4][DEP], const float (&z)[DEP], float (&v)[4]) {
+  v[0] = qv.x; v[1] = qv.y; v[2] = qv.z; v[3] = qv.w;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    float a = 0.f;
+#pragma unroll
+    for (int j = 0; j < DEP; j++) a += w[k][j] * z[j];
+    v[k] += a;
+  }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void store4(float* __restrict__ row, int cb, int d, const float (&x)[4]) {
+  if (VEC) *(float4*)(row + cb) = make_float4(x[0], x[1], x[2], x[3]);
+  else {
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (cb + k < d) row[cb + k] = x[k];
+  }
+}
+
+template <int CS, int DEP, bool VEC, bool STD>
+__global__ __launch_bounds__(256) void k_mpnn_bwd_coef(const float* __restrict__ dM, int64_t lddm, const float* __restrict__ Q,
+                                                      int64_t ldq, const float* __restrict__ We, int64_t ldwe,
+                                                      const float* __restrict__ ea, int de, const int32_t* __restrict__ rowptr,
+                                                      const int32_t* __restrict__ src, const int32_t* __restrict__ node_order,
+                                                      int64_t n, int d, float* __restrict__ coef) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int64_t n_slots = (int64_t)gridDim.x * (blockDim.x >> 6) / CS;
+  const int cg = lane + 64 * (int)(wave % CS);
+  if (cg >= ((d + 3) >> 2)) return;
+  const int cb = cg * 4;
+  float w[4][DEP];
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+#pragma unroll
+    for (int j = 0; j < DEP; j++) w[k][j] = (j < de && cb + k < d) ? We[(int64_t)(cb + k) * ldwe + j] : 0.f;
+  for (int64_t p = wave / CS; p < n; p += n_slots) {
+    const int r0 = rowptr[p], r1 = rowptr[p + 1];
+    if (r1 == r0) continue;                            // (no edge reads the coefficients of a target without edges)
+    const int64_t t = node_order ? (int64_t)node_order[p] : p;
+    // Two trips over the segment (its rows are in L2 after the first).  Trip 1: the forward's shift by the first message gives a
+    // first mean; but its running sum drifts by (m_0 - mean) per edge, and the rounding of a long segment's sum then shows in
+    // m_e - mean wherever an edge sits close to the mean.  Trip 2 sums the messages CENTRED on that first mean: the correction of
+    // the mean and the variance both come from sums that stay near zero.
+    float m0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+    const float fc = (float)(r1 - r0);
+    for (int trip = 0; trip < 2; trip++) {
+      for (int e = r0; e < r1; e++) {
+        float z[DEP], v[4];
+#pragma unroll
+        for (int j = 0; j < DEP; j++) z[j] = (j < de) ? ea[(int64_t)e * de + j] : 0.f;
+        bwd_message<DEP>(load4<VEC>(Q + (int64_t)src[e] * ldq, cb, d), w, z, v);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          if (trip == 0 && e == r0) m0[k] = v[k];
+          const float dd = v[k] - m0[k];
+          s1[k] += dd;
+          if (trip == 1) s2[k] = __builtin_fmaf(dd, dd, s2[k]);
+        }
+      }
+      if (trip == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) { m0[k] += s1[k] / fc; s1[k] = 0.f; }      // (from here on m0 is the first mean)
+      }
+    }
+    const float4 g4 = load4<VEC>(dM + t * lddm, cb, d);
+    const float g[4] = {g4.x, g4.y, g4.z, g4.w};
+    float A[4], mean[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const float mu = s1[k] / fc;
+      mean[k] = m0[k] + mu;
+      if (STD) {
+        const float var = s2[k] / fc - mu * mu;
+        A[k] = (var > 0.f) ? g[k] / (fc * sqrtf(var + 1e-5f)) : 0.f;   // (relu'(var) = 0 at var <= 0)
+      } else {
+        A[k] = g[k] * (2.f / fc);
+      }
+    }
+    store4<VEC>(coef + t * (int64_t)d, cb, d, A);
+    store4<VEC>(coef + (n + t) * (int64_t)d, cb, d, mean);
+  }
+}
+
+template <int CS, int DEP, bool VEC>
+__global__ __launch_bounds__(256) void k_mpnn_bwd_edge_var(const float* __restrict__ coef, const float* __restrict__ Q, int64_t ldq,
+                                                          const float* __restrict__ We, int64_t ldwe, const float* __restrict__ ea,
+                                                          int de, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src,
+                                                          const int32_t* __restrict__ node_order, int64_t n, int d, int64_t n_edges,
+                                                          float* __restrict__ dea, float* __restrict__ dWe) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int64_t n_slots = (int64_t)gridDim.x * (blockDim.x >> 6) / CS;   // == rgnn_mpnn_bwd_slots(n)
+  const int cg = lane + 64 * (int)(wave % CS);
+  const bool act = cg < ((d + 3) >> 2);
+  const int cb = act ? cg * 4 : 0;
+  float* dea_w = dea + (wave % CS) * n_edges * de;     // (CS > 1: slice h of [CS, E, de], summed by k_reduce_slots)
+  constexpr int BUF = 32;                              // results wait in LDS and are flushed together, as in k_mpnn_bwd_edge
+  __shared__ float buf_v[4][BUF][DEP];
+  __shared__ int buf_e[4][BUF];
+  const int wib = threadIdx.x >> 6;
+  int n_buf = 0;
+  auto flush = [&]() {
+    for (int i = lane; i < n_buf * DEP; i += 64) {
+      const int r = i / DEP, c = i % DEP;
+      if (c < de) dea_w[(int64_t)buf_e[wib][r] * de + c] = buf_v[wib][r][c];
+    }
+    n_buf = 0;
+  };
+  float w[4][DEP], dw[4][DEP];
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+#pragma unroll
+    for (int j = 0; j < DEP; j++) {
+      w[k][j] = (act && j < de && cb + k < d) ? We[(int64_t)(cb + k) * ldwe + j] : 0.f;
+      dw[k][j] = 0.f;
+    }
+  for (int64_t p = wave / CS; p < n; p += n_slots) {
+    const int r0 = rowptr[p], r1 = rowptr[p + 1];
+    if (r1 == r0) continue;
+    const int64_t t = node_order ? (int64_t)node_order[p] : p;
+    float4 A4 = make_float4(0.f, 0.f, 0.f, 0.f), mu4 = A4;
+    if (act) {
+      A4 = load4<VEC>(coef + t * (int64_t)d, cb, d);
+      mu4 = load4<VEC>(coef + (n + t) * (int64_t)d, cb, d);
+    }
+    const float A[4] = {A4.x, A4.y, A4.z, A4.w}, mu[4] = {mu4.x, mu4.y, mu4.z, mu4.w};
+    for (int e = r0; e < r1; e++) {
+      float z[DEP], dz[DEP], v[4];
+#pragma unroll
+      for (int j = 0; j < DEP; j++) { z[j] = (j < de) ? ea[(int64_t)e * de + j] : 0.f; dz[j] = 0.f; }
+      float4 qv = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (act) qv = load4<VEC>(Q + (int64_t)src[e] * ldq, cb, d);
+      bwd_message<DEP>(qv, w, z, v);
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const float gg = A[k] * (v[k] - mu[k]);        // (inactive lanes and channels past d: A = 0)
+#pragma unroll
+        for (int j = 0; j < DEP; j++) { dz[j] += gg * w[k][j]; dw[k][j] += gg * z[j]; }
+      }
+      int comp;
+      const float tot = wave_reduce_vec<DEP>(dz, lane, comp);
+      if (lane < DEP) buf_v[wib][n_buf][comp] = tot;
+      if (lane == 0) buf_e[wib][n_buf] = e;
+      if (++n_buf == BUF) flush();                     // (same wave wrote and reads: LDS operations stay in order)
+    }
+  }
+  flush();
+  if (act && wave / CS < n_slots) {                    // per-slot partial of dW_e (plain stores; k_reduce_slots sums the slots)
+    float* o = dWe + (wave / CS) * (int64_t)d * de;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+#pragma unroll
+      for (int j = 0; j < DEP; j++)
+        if (j < de && cb + k < d) o[(int64_t)(cb + k) * de + j] = dw[k][j];
+  }
+}
+
+template <int DEP, bool VEC>
+__global__ __launch_bounds__(256) void k_mpnn_bwd_src_var(const float* __restrict__ coef, const float* __restrict__ Q, int64_t ldq,
+                                                         const float* __restrict__ We, int64_t ldwe, const float* __restrict__ ea,
+                                                         int de, const int32_t* __restrict__ rowptr_s, const int32_t* __restrict__ tnode,
+                                                         const int32_t* __restrict__ tpos, const int32_t* __restrict__ node_order,
+                                                         int64_t n, int d, float* __restrict__ dQ, int64_t lddq) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int64_t n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  const int groups = (d + 3) >> 2;
+  // one channel group (of 4) per lane at a time: its W_e slice is 4 x DEP registers whatever the message width
+  for (int cg = lane; cg < groups; cg += 64) {
+    const int cb = cg * 4;
+    float w[4][DEP];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+#pragma unroll
+      for (int j = 0; j < DEP; j++) w[k][j] = (j < de && cb + k < d) ? We[(int64_t)(cb + k) * ldwe + j] : 0.f;
+    for (int64_t p = wave; p < n; p += n_waves) {
+      const int r0 = rowptr_s[p], r1 = rowptr_s[p + 1];
+      const int64_t s = node_order ? (int64_t)node_order[p] : p;
+      float acc[4] = {0.f, 0.f, 0.f, 0.f};
+      if (r1 > r0) {
+        const float4 qs = load4<VEC>(Q + s * ldq, cb, d);
+        for (int j = r0; j < r1; j++) {
+          const int64_t t = tnode[j];
+          const int64_t e = tpos[j];
+          float z[DEP], v[4];
+#pragma unroll
+          for (int i = 0; i < DEP; i++) z[i] = (i < de) ? ea[e * de + i] : 0.f;
+          bwd_message<DEP>(qs, w, z, v);
+          const float4 A = load4<VEC>(coef + t * (int64_t)d, cb, d);
+          const float4 mu = load4<VEC>(coef + (n + t) * (int64_t)d, cb, d);
+          acc[0] += A.x * (v[0] - mu.x); acc[1] += A.y * (v[1] - mu.y);
+          acc[2] += A.z * (v[2] - mu.z); acc[3] += A.w * (v[3] - mu.w);
+        }
+      }
+      store4<VEC>(dQ + s * lddq, cb, d, acc);
+    }
+  }
+}
+
+// Backward of rgnn_segment_reduce for min | var | std (codes 3 - 5) over the rows of a segment: min -> the first row attaining
+// the minimum; var / std -> A (row - mean) with the coefficients above, from the shifted sums of the forward kernel.
+template <int AGGR>
+__global__ __launch_bounds__(256) void k_segment_reduce_bwd_ext(const float* __restrict__ dM, int64_t lddm,
+                                                               const float* __restrict__ rows, int64_t ldr,
+                                                               const int32_t* __restrict__ rowptr, const int32_t* __restrict__ order,
+                                                               int64_t n, int d, float* __restrict__ drows, int64_t lddr) {
+  const int lane = threadIdx.x & 63;
+  const int64_t pos = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (pos >= n) return;
+  const int64_t node = order ? (int64_t)order[pos] : pos;
+  const int beg = rowptr[pos], end = rowptr[pos + 1];
+  if (end == beg) return;
+  const float fc = (float)(end - beg);
+  for (int c = lane; c < d; c += 64) {
+    const float g = dM[node * lddm + c];
+    if (AGGR == RGNN_AGGR_MIN) {
+      float best = INFINITY;
+      int arg = beg;
+      for (int e = beg; e < end; e++) {
+        const float v = rows[(int64_t)e * ldr + c];
+        if (v < best) { best = v; arg = e; }
+      }
+      for (int e = beg; e < end; e++) drows[(int64_t)e * lddr + c] = (e == arg) ? g : 0.f;
+    } else {
+      float r0 = rows[(int64_t)beg * ldr + c];           // trip 1: shift by the first row -> a first mean; trip 2: centred on it
+      float s1 = 0.f, s2 = 0.f;                          // (as in k_mpnn_bwd_coef)
+      for (int e = beg; e < end; e++) s1 += rows[(int64_t)e * ldr + c] - r0;
+      r0 += s1 / fc;
+      s1 = 0.f;
+      for (int e = beg; e < end; e++) {
+        const float dd = rows[(int64_t)e * ldr + c] - r0;
+        s1 += dd;
+        s2 = __builtin_fmaf(dd, dd, s2);
+      }
+      const float mu = s1 / fc;                          // (mean = r0 + mu, never formed: the rows are shifted by r0 again below)
+      float A = g * (2.f / fc);
+      if (AGGR == RGNN_AGGR_STD) {
+        const float var = s2 / fc - mu * mu;
+        A = (var > 0.f) ? g / (fc * sqrtf(var + 1e-5f)) : 0.f;
+      }
+      for (int e = beg; e < end; e++) drows[(int64_t)e * lddr + c] = A * ((rows[(int64_t)e * ldr + c] - r0) - mu);
+    }
+  }
+}
+
 // out[i] = sum_s part[s, i]: one block = 64 columns x 16 slot groups (coalesced 256-B reads), LDS combine
 __global__ __launch_bounds__(1024) void k_reduce_slots(const float* __restrict__ part, int64_t slots, int64_t width,
                                                       float* __restrict__ out) {
@@ -916,16 +1177,37 @@ void launch_bwd(int mode, dim3 g, dim3 b, hipStream_t s, const BwdArgs& a) {
     hipLaunchKernelGGL((k_mpnn_bwd_arg<CS, DEP, VEC>), dim3(g.x * 4), b, 0, s, a.Q, a.ldq, a.We, a.ldwe, a.ea, a.de, a.rowptr,
                        a.src, a.node_order, a.n, a.d, a.arg);
     if (a.de > 0) RGNN_EDGE(0);
+  } else if (mode == RGNN_AGGR_MIN) {                  // the same machinery, the comparison turned round
+    hipLaunchKernelGGL((k_mpnn_bwd_arg<CS, DEP, VEC, false, true>), dim3(g.x * 4), b, 0, s, a.Q, a.ldq, a.We, a.ldwe, a.ea, a.de,
+                       a.rowptr, a.src, a.node_order, a.n, a.d, a.arg);
+    if (a.de > 0) RGNN_EDGE(0);
+  } else if (mode == RGNN_AGGR_VAR || mode == RGNN_AGGR_STD) {
+    float* coef = (float*)a.arg;                        // float [2, n, d]: A | mean
+    if (mode == RGNN_AGGR_STD)
+      hipLaunchKernelGGL((k_mpnn_bwd_coef<CS, DEP, VEC, true>), dim3(g.x * 4), b, 0, s, a.dM, a.lddm, a.Q, a.ldq, a.We, a.ldwe, a.ea,
+                         a.de, a.rowptr, a.src, a.node_order, a.n, a.d, coef);
+    else
+      hipLaunchKernelGGL((k_mpnn_bwd_coef<CS, DEP, VEC, false>), dim3(g.x * 4), b, 0, s, a.dM, a.lddm, a.Q, a.ldq, a.We, a.ldwe, a.ea,
+                         a.de, a.rowptr, a.src, a.node_order, a.n, a.d, coef);
+    if (a.de > 0)
+      hipLaunchKernelGGL((k_mpnn_bwd_edge_var<CS, DEP, VEC>), g, b, 0, s, (const float*)coef, a.Q, a.ldq, a.We, a.ldwe, a.ea, a.de,
+                         a.rowptr, a.src, a.node_order, a.n, a.d, a.n_edges, a.dea, a.dWe);
   } else if (a.de > 0) {
     if (mode == RGNN_AGGR_MEAN) RGNN_EDGE(1); else RGNN_EDGE(2);
   }
 #undef RGNN_EDGE
 }
 
+template <int DEP, bool VEC>
+void launch_src_var(dim3 g, dim3 b, hipStream_t s, const BwdArgs& a) {
+  hipLaunchKernelGGL((k_mpnn_bwd_src_var<DEP, VEC>), g, b, 0, s, (const float*)a.arg, a.Q, a.ldq, a.We, a.ldwe, a.ea, a.de, a.rowptr_s,
+                     a.tnode, a.tpos, a.node_order, a.n, a.d, a.dQ, a.lddq);
+}
+
 template <int NCH, bool VEC>
 void launch_src(int mode, dim3 g, dim3 b, hipStream_t s, const BwdArgs& a) {
 #define RGNN_SRC(M) hipLaunchKernelGGL((k_mpnn_bwd_src<NCH, M, VEC>), g, b, 0, s, a.dM, a.lddm, a.arg, a.target_scale, a.rowptr_s, a.tnode, a.tpos, a.node_order, a.n, a.d, a.dQ, a.lddq)
-  if (mode == RGNN_AGGR_MAX) RGNN_SRC(0);
+  if (mode == RGNN_AGGR_MAX || mode == RGNN_AGGR_MIN) RGNN_SRC(0);
   else if (mode == RGNN_AGGR_MEAN) RGNN_SRC(1);
   else RGNN_SRC(2);
 #undef RGNN_SRC
@@ -1002,8 +1284,9 @@ extern "C" int rgnn_mpnn_aggregate_bwd(const float* dM, int64_t lddm, const floa
   RGNN_CHECK_ARG(dM && Q && rowptr_t && src_sorted && dQ && rowptr_s && tnode && tpos, "null pointers");
   RGNN_CHECK_ARG(de >= 0 && de <= 16, "edge attribute width must be <= 16");
   RGNN_CHECK_ARG(de == 0 || (edge_attr_sorted && d_edge_attr && We && dWe && dwe_partial), "edge attribute pointers");
-  RGNN_CHECK_ARG(aggr >= 0 && aggr <= 2, "unknown aggregation");
-  RGNN_CHECK_ARG(aggr != RGNN_AGGR_MAX || arg_tmp, "max aggregation needs the arg workspace");
+  RGNN_CHECK_ARG(aggr >= 0 && aggr <= RGNN_AGGR_STD, "unknown aggregation");
+  RGNN_CHECK_ARG((aggr != RGNN_AGGR_MAX && aggr != RGNN_AGGR_MIN) || arg_tmp, "max / min aggregation needs the arg workspace");
+  RGNN_CHECK_ARG((aggr != RGNN_AGGR_VAR && aggr != RGNN_AGGR_STD) || arg_tmp, "var / std aggregation needs the coefficient workspace");
   RGNN_CHECK_ARG(aggr != RGNN_AGGR_MEAN || target_scale, "mean aggregation needs 1 / in-degree per node");
   RGNN_CHECK_ARG(d <= 1024, "message width must be <= 1024");
   const bool vec = d % 4 == 0 && lddm % 4 == 0 && ldq % 4 == 0 && lddq % 4 == 0 &&
@@ -1024,7 +1307,11 @@ extern "C" int rgnn_mpnn_aggregate_bwd(const float* dM, int64_t lddm, const floa
     if (de <= 4) launch_bwd<CS, 4, V>(aggr, ge, b, s, a);                   \
     else if (de <= 8) launch_bwd<CS, 8, V>(aggr, ge, b, s, a);              \
     else launch_bwd<CS, 16, V>(aggr, ge, b, s, a);                          \
-    launch_src<NCH, V>(aggr, g, b, s, a);                                   \
+    if (aggr == RGNN_AGGR_VAR || aggr == RGNN_AGGR_STD) {                   \
+      if (de <= 4) launch_src_var<4, V>(g, b, s, a);                        \
+      else if (de <= 8) launch_src_var<8, V>(g, b, s, a);                   \
+      else launch_src_var<16, V>(g, b, s, a);                               \
+    } else launch_src<NCH, V>(aggr, g, b, s, a);                            \
   } while (0)
 #define RGNN_BWD(NCH) do { if (vec) RGNN_BWD2(NCH, true); else RGNN_BWD2(NCH, false); } while (0)
   switch (nch) {
@@ -1124,9 +1411,16 @@ extern "C" int rgnn_segment_reduce_bwd(const float* dM, int64_t lddm, const floa
                                        int64_t lddr, rgnn_stream_t stream) {
   if (n == 0 || d == 0) return RGNN_OK;
   RGNN_CHECK_ARG(dM && rows && rowptr_t && d_rows, "null pointers");
-  RGNN_CHECK_ARG(aggr >= 0 && aggr <= 2, "unknown aggregation");
-  hipLaunchKernelGGL(k_segment_reduce_bwd, dim3(rgnn_blocks(n, 4)), dim3(256), 0, (hipStream_t)stream, dM, lddm, rows, ldr,
-                     rowptr_t, node_order, n, d, aggr, d_rows, lddr);
+  RGNN_CHECK_ARG(aggr >= 0 && aggr <= RGNN_AGGR_STD, "unknown aggregation");
+#define RGNN_SRBX(A) hipLaunchKernelGGL((k_segment_reduce_bwd_ext<A>), dim3(rgnn_blocks(n, 4)), dim3(256), 0, (hipStream_t)stream, dM, \
+                                        lddm, rows, ldr, rowptr_t, node_order, n, d, d_rows, lddr)
+  if (aggr == RGNN_AGGR_MIN) RGNN_SRBX(RGNN_AGGR_MIN);
+  else if (aggr == RGNN_AGGR_VAR) RGNN_SRBX(RGNN_AGGR_VAR);
+  else if (aggr == RGNN_AGGR_STD) RGNN_SRBX(RGNN_AGGR_STD);
+  else
+    hipLaunchKernelGGL(k_segment_reduce_bwd, dim3(rgnn_blocks(n, 4)), dim3(256), 0, (hipStream_t)stream, dM, lddm, rows, ldr,
+                       rowptr_t, node_order, n, d, aggr, d_rows, lddr);
+#undef RGNN_SRBX
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
 }

@@ -376,6 +376,21 @@ def aggregate(Q, We, ea_sorted, graph, aggr: str):
     return AggregateFn.apply(Q, We, ea_sorted, graph, aggr)
 
 
+class ZeroGradFn(torch.autograd.Function):
+    """y = x, with ``t`` kept on the tape at gradient exactly 0: a term that drops out of the result (the bias under the var / std
+    aggregation) still hands its parameters a zero gradient instead of none, as autograd through the reference's layers does."""
+
+    @staticmethod
+    def forward(ctx, x, t):
+        ctx.save_for_backward(t)
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (t,) = ctx.saved_tensors
+        return dy, torch.zeros_like(t)
+
+
 class SegmentReduceFn(torch.autograd.Function):
     """M[t] = aggr over the rows of segment t (general message path, pre_layers > 1)."""
 

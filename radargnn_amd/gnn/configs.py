@@ -26,7 +26,7 @@ class GNNArchitectureConfig:
     conv_pre_mlp_layer_number: int = 1
     conv_post_mlp_layer_number: int = 1
     conv_use_edge_encoder: bool = False
-    aggregation_function: str = "max"          # "max" | "mean" | "add"
+    aggregation_function: str = "max"          # "max" | "mean" | "add" ("sum") | "min" | "var" | "std"
 
 
 # class order of the two datasets' label columns, and the weight a class gets when the configuration names none

@@ -4,8 +4,9 @@ keys), with the message passing done by librgnn's fused kernels instead of torch
 gather -> cat -> Linear -> scatter.
 
 Semantics kept from torch_geometric 2.1 ``MessagePassing`` (flow source_to_target): ``x_j = x[edge_index[0]]``,
-``x_i = x[edge_index[1]]``, messages are reduced at ``edge_index[1]``; aggregation max | mean | add, empty
-segments give 0.
+``x_i = x[edge_index[1]]``, messages are reduced at ``edge_index[1]``; aggregation max | mean | add (sum) | min | var | std, empty
+segments give 0 (std: sqrt(1e-5); var = mean(m^2) - mean(m)^2 unclamped, std = sqrt(relu(var) + 1e-5) as in PyG 2.1's
+``nn/aggr/basic.py``).  Any other name of PyG's resolver (softmax, mul, median, powermean, a list of aggregators) raises ValueError.
 
 How the message function is evaluated.  With ``pre_layers == 1`` (the shipped setting) the message MLP is one
 Linear over ``cat[x_i, x_j, e]`` with weight ``W = [W_i | W_j | W_e]`` (column layout of mpnn_layers.py:98), and
@@ -14,7 +15,8 @@ Linear over ``cat[x_i, x_j, e]`` with weight ``W = [W_i | W_j | W_e]`` (column l
 
 so the [E, D] x [D, D] product of the reference becomes two node-wise projections P = x W_i^T + b and
 Q = x W_j^T (one MFMA launch) plus a fused gather / de x D mat-vec / segmented reduce over the CSR keyed on the
-target (rgnn_mpnn_aggregate).  Real-arithmetic identical; fp32 deviation ~1e-6 (tests/test_gpu_gnn.py).
+target (rgnn_mpnn_aggregate).  Real-arithmetic identical; fp32 deviation ~1e-6 (tests/test_gpu_gnn.py).  (.) is + on targets with
+edges for max | mean | min, deg * for add, and nothing at all for var | std: they are invariant under a shift of a segment's messages.
 With ``pre_layers > 1`` the first layer is evaluated per edge the same way (rgnn_mpnn_edge_hidden), the
 remaining Linear layers run on the [E, D] rows and rgnn_segment_reduce aggregates.
 """
@@ -399,6 +401,8 @@ class _ConvBase(nn.Module):
                 # (rgnn_mpnn_aggregate_win) instead of one row gather per edge
                 return ops.mpnn_aggregate_win(p_bias, Q, We, ea_sorted, graph.rowptr, graph.src, graph.win_plan(),
                                               node_order=graph.order, skip_empty_rows=skip_empty_rows)
+            if self.aggr in ops.SHIFT_INVARIANT_AGGR:
+                P = p_bias = None                   # var / std: the target term and the bias drop out (the kernel would not read them)
             return ops.mpnn_aggregate(P, p_bias, Q, We, ea_sorted, graph.rowptr, graph.src, self.aggr,
                                       node_order=graph.order, chunks=graph.chunks, skip_empty_rows=skip_empty_rows)
         if wide:
@@ -432,6 +436,8 @@ class _ConvBase(nn.Module):
                 hidden = AG.linear(hidden, lin.weight, lin.bias, relu=j != len(linears) - 2)
             return AG.SegmentReduceFn.apply(hidden, graph, self.aggr)
         M = AG.aggregate(Q, We, ea_sorted, graph, self.aggr)
+        if self.aggr in ops.SHIFT_INVARIANT_AGGR:   # var / std of P + b + q_e = var / std of q_e: nothing is added, dP = dp_bias = 0
+            return M if p_bias is None else AG.ZeroGradFn.apply(M, p_bias)       # (P is a slice of the [P | Q] launch: on the tape)
         term = P
         if p_bias is not None:
             term = p_bias.view(1, -1) if term is None else term + p_bias.view(1, -1)
@@ -462,7 +468,7 @@ class MPNNConv(_ConvBase):
     def __init__(self, in_channels: int, out_channels: int, edge_dim: int, aggr: str = "max",
                  pre_layers: int = 1, post_layers: int = 1, use_edge_encoder: bool = False):
         super().__init__()
-        if aggr not in ops.AGGR_CODES:
+        if not isinstance(aggr, str) or aggr not in ops.AGGR_CODES:   # (softmax, mul, median, powermean, lists of aggregators: not built)
             raise ValueError(f"unknown aggregation {aggr!r}")
         self.aggr = aggr
         self.in_channels = in_channels
@@ -760,7 +766,7 @@ class RadarPointGNNConv(_ConvBase):
     def __init__(self, init_node_dim: int, init_edge_dim: int, aggr: str = "max", pre_layers: int = 1,
                  post_layers: int = 1):
         super().__init__()
-        if aggr not in ops.AGGR_CODES:
+        if not isinstance(aggr, str) or aggr not in ops.AGGR_CODES:   # (softmax, mul, median, powermean, lists of aggregators: not built)
             raise ValueError(f"unknown aggregation {aggr!r}")
         self.aggr = aggr
         self.in_channels = init_node_dim

@@ -24,7 +24,9 @@ NODE_FEATURE_CODES = {"rcs": 0, "time_index": 1, "degree": 2, "velocity_vector_l
                       "spatial_coordinates": 5}
 NODE_FEATURE_WIDTH = {"rcs": 1, "time_index": 1, "degree": 1, "velocity_vector_length": 1, "velocity_vector": 2,
                       "spatial_coordinates": 2}
-AGGR_CODES = {"max": 0, "mean": 1, "add": 2, "sum": 2}
+AGGR_CODES = {"max": 0, "mean": 1, "add": 2, "sum": 2, "min": 3, "var": 4, "std": 5}     # RGNN_AGGR_* (rgnn.h)
+SHIFT_INVARIANT_AGGR = ("var", "std")     # the target term and the bias drop out of these: P / p_bias are ignored, dP = dp_bias = 0
+STD_EPS = 1e-5                            # std = sqrt(relu(var) + STD_EPS): an empty segment gives sqrt(STD_EPS), not 0
 MAX_FUSED_EDGE_WIDTH = 32        # edge attributes per edge the fused message kernels take (rgnn_mpnn_aggregate / _edge_hidden)
 MAX_FUSED_EDGE_WIDTH_BWD = 16    # ... and their backward (rgnn_mpnn_aggregate_bwd)
 
@@ -1409,6 +1411,8 @@ def mpnn_aggregate(P, p_bias, Q, We, ea_sorted, rowptr_t, src_sorted, aggr: str,
                    node_order: Optional[torch.Tensor] = None, chunks: Optional[torch.Tensor] = None,
                    skip_empty_rows: bool = False) -> torch.Tensor:
     """m[t] = P[t] (+p_bias) (.) reduce_{e -> t}( Q[src_e] + We a_e ); empty segments -> 0.
+    ``aggr``: max | mean | add (sum) | min | var | std.  var / std are invariant under a shift of a segment's messages: ``P`` and
+    ``p_bias`` are ignored for them (the kernel never reads them); std = sqrt(relu(var) + 1e-5), sqrt(1e-5) on empty segments.
     ``skip_empty_rows``: the caller never reads the rows of targets without incoming edges; they may stay unwritten."""
     P, Q, We, ea_sorted, de = _mp_common(P, p_bias, Q, We, ea_sorted, rowptr_t, src_sorted)
     n, d = rowptr_t.numel() - 1, Q.shape[1]
@@ -1519,8 +1523,9 @@ def segment_reduce(rows: torch.Tensor, rowptr_t: torch.Tensor, aggr: str,
                    node_order: Optional[torch.Tensor] = None) -> torch.Tensor:
     rows = _rowmajor(_dev(rows, "rows", torch.float32), "rows")
     n, d = rowptr_t.numel() - 1, rows.shape[1]
-    if rows.shape[0] == 0:                                # (no rows: every segment is empty -> exactly 0, torch-scatter's convention)
-        return torch.zeros((n, d), dtype=torch.float32, device=rows.device)
+    if rows.shape[0] == 0:                                # (no rows: every segment is empty -> exactly 0, torch-scatter's convention;
+        fill = torch.tensor(STD_EPS, dtype=torch.float32).sqrt().item() if aggr == "std" else 0.0          # std: sqrt(0 + 1e-5))
+        return torch.full((n, d), fill, dtype=torch.float32, device=rows.device)
     out = torch.empty((n, d), dtype=torch.float32, device=rows.device)
     check(lib.rgnn_segment_reduce(_ptr(rows), _ld(rows), _ptr(rowptr_t), _ptr(node_order), n, d, AGGR_CODES[aggr],
                                   _ptr(out), d, _stream()))
@@ -1595,7 +1600,9 @@ def mpnn_aggregate_bwd(dM, Q, We, ea_sorted, rowptr_t, src_sorted, aggr: str, so
     the shapes they cover; ``arg``: the winners the forward pass recorded (uint16 in-segment indices; else recomputed).
     ``arg_out`` (tests: which edges the gradient went to): a caller-owned [n, d] buffer the launch recomputes its winners into,
     int32 CSR positions on the generic kernel, int16 (uint16) in-segment indices on the lane-local one; not written when ``arg``
-    is given or the aggregation is not max."""
+    is given or the aggregation is not max.
+    min: the generic max kernels with the comparison turned round.  var / std: every edge receives A[t] (m_e - mean[t]) with m_e
+    recomputed; A and mean come from a pre-pass into a float [2, n, d] workspace (no ``arg`` buffer, no ``target_scale``)."""
     dM = _rowmajor(_dev(dM, "dM", torch.float32), "dM")
     _, Q, We, ea_sorted, de = _mp_common(None, None, Q, We, ea_sorted, rowptr_t, src_sorted)
     n, d = rowptr_t.numel() - 1, Q.shape[1]
@@ -1637,8 +1644,10 @@ def mpnn_aggregate_bwd(dM, Q, We, ea_sorted, rowptr_t, src_sorted, aggr: str, so
     dWe = torch.empty((d, de), dtype=torch.float32, device=dev) if de else None
     part = torch.empty((int(lib.rgnn_mpnn_bwd_slots(n)), d, de), dtype=torch.float32, device=dev) if de else None
     arg = None
-    if AGGR_CODES[aggr] == 0:
+    if aggr in ("max", "min"):
         arg = torch.empty((n, d), dtype=torch.int32, device=dev) if arg_out is None else _arg_buffer(arg_out, n, d, torch.int32)
+    elif aggr in SHIFT_INVARIANT_AGGR:
+        arg = torch.empty((2, n, d), dtype=torch.float32, device=dev)      # coefficient workspace: A | mean per (target, channel)
     if AGGR_CODES[aggr] == 1:
         _dev(target_scale, "target_scale", torch.float32)
     check(lib.rgnn_mpnn_aggregate_bwd(_ptr(dM), _ld(dM), _ptr(Q), _ld(Q), _ptr(We), 0 if We is None else _ld(We),
