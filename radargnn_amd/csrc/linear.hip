@@ -637,7 +637,11 @@ __global__ __launch_bounds__(WGM * WGN * 64) void k_linear_x3(const LinParams p)
   load_next(rx); advance_loads();               // step 2 (NSETS == 1: step 1)
   // step g: multiply from buffer g & 1 while the operands of step g + 1 (register set `r`) go into the other buffer and
   // `r` is re-requested for step g + 3.  Returns false after the last tile.
-  auto step = [&](Regs& r, const char* cur, char* nxt) -> bool {
+  // (always_inline: left to itself hipcc 7.2 keeps `step` a real function in the two 256 x 256 instances, large enough to need
+  //  long branches, and takes s[30:31] -- the function's return address -- as their scratch pair without saving it where nothing
+  //  else uses it: the IDX instance then returned to its own return block for ever.  tests/test_gpu_dense_fwd_edges.py:
+  //  x3_n256_k36_rows)
+  auto step = [&](Regs& r, const char* cur, char* nxt) __attribute__((always_inline)) -> bool {
     __syncthreads();    // buffer `cur` is complete; nobody reads `nxt` (last multiplied in step g - 1) any more
     store_regs(r, nxt);
     load_next(r);
