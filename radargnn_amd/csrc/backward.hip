@@ -893,13 +893,14 @@ __global__ __launch_bounds__(256) void k_mpnn_bwd_src_var(const float* __restric
   }
 }
 
-// Backward of rgnn_segment_reduce for min | var | std (codes 3 - 5) over the rows of a segment: min -> the first row attaining
-// the minimum; var / std -> A (row - mean) with the coefficients above, from the shifted sums of the forward kernel.
+// Backward of rgnn_segment_reduce (general message path, pre_layers > 1): rows [E, d] in CSR-by-target order were reduced per segment.
+// max / min: dM[t, c] goes to the FIRST row of the segment attaining the extremum (one search, the comparison turned round);
+// mean / add: to every row; var / std: A (row - mean) with the coefficients above, from the shifted sums of the forward kernel.
 template <int AGGR>
-__global__ __launch_bounds__(256) void k_segment_reduce_bwd_ext(const float* __restrict__ dM, int64_t lddm,
-                                                               const float* __restrict__ rows, int64_t ldr,
-                                                               const int32_t* __restrict__ rowptr, const int32_t* __restrict__ order,
-                                                               int64_t n, int d, float* __restrict__ drows, int64_t lddr) {
+__global__ __launch_bounds__(256) void k_segment_reduce_bwd(const float* __restrict__ dM, int64_t lddm,
+                                                           const float* __restrict__ rows, int64_t ldr,
+                                                           const int32_t* __restrict__ rowptr, const int32_t* __restrict__ order,
+                                                           int64_t n, int d, float* __restrict__ drows, int64_t lddr) {
   const int lane = threadIdx.x & 63;
   const int64_t pos = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (pos >= n) return;
@@ -909,14 +910,17 @@ __global__ __launch_bounds__(256) void k_segment_reduce_bwd_ext(const float* __r
   const float fc = (float)(end - beg);
   for (int c = lane; c < d; c += 64) {
     const float g = dM[node * lddm + c];
-    if (AGGR == RGNN_AGGR_MIN) {
-      float best = INFINITY;
+    if (AGGR == RGNN_AGGR_MAX || AGGR == RGNN_AGGR_MIN) {
+      float best = (AGGR == RGNN_AGGR_MAX) ? -INFINITY : INFINITY;
       int arg = beg;
       for (int e = beg; e < end; e++) {
         const float v = rows[(int64_t)e * ldr + c];
-        if (v < best) { best = v; arg = e; }
+        if ((AGGR == RGNN_AGGR_MAX) ? (v > best) : (v < best)) { best = v; arg = e; }
       }
       for (int e = beg; e < end; e++) drows[(int64_t)e * lddr + c] = (e == arg) ? g : 0.f;
+    } else if (AGGR == RGNN_AGGR_MEAN || AGGR == RGNN_AGGR_ADD) {
+      const float sc = (AGGR == RGNN_AGGR_MEAN) ? 1.f / fc : 1.f;
+      for (int e = beg; e < end; e++) drows[(int64_t)e * lddr + c] = g * sc;
     } else {
       float r0 = rows[(int64_t)beg * ldr + c];           // trip 1: shift by the first row -> a first mean; trip 2: centred on it
       float s1 = 0.f, s2 = 0.f;                          // (as in k_mpnn_bwd_coef)
@@ -1015,35 +1019,6 @@ __global__ __launch_bounds__(256) void k_mpnn_bwd_src(const float* __restrict__ 
         if (cb + 2 < d) o[2] = acc[q].z;
         if (cb + 3 < d) o[3] = acc[q].w;
       }
-    }
-  }
-}
-
-// Backward of rgnn_segment_reduce (general message path, pre_layers > 1): rows [E, d] in CSR-by-target order were
-// reduced per segment.  max: dM[t, c] goes to the first row of the segment attaining the maximum; mean / add: to every row.
-__global__ __launch_bounds__(256) void k_segment_reduce_bwd(const float* __restrict__ dM, int64_t lddm,
-                                                           const float* __restrict__ rows, int64_t ldr,
-                                                           const int32_t* __restrict__ rowptr, const int32_t* __restrict__ order,
-                                                           int64_t n, int d, int aggr, float* __restrict__ drows, int64_t lddr) {
-  const int lane = threadIdx.x & 63;
-  const int64_t pos = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (pos >= n) return;
-  const int64_t node = order ? (int64_t)order[pos] : pos;
-  const int beg = rowptr[pos], end = rowptr[pos + 1];
-  if (end == beg) return;
-  const float sc = (aggr == RGNN_AGGR_MEAN) ? 1.f / (float)(end - beg) : 1.f;
-  for (int c = lane; c < d; c += 64) {
-    const float g = dM[node * lddm + c];
-    if (aggr == RGNN_AGGR_MAX) {
-      float best = -INFINITY;
-      int arg = beg;
-      for (int e = beg; e < end; e++) {
-        const float v = rows[(int64_t)e * ldr + c];
-        if (v > best) { best = v; arg = e; }
-      }
-      for (int e = beg; e < end; e++) drows[(int64_t)e * lddr + c] = (e == arg) ? g : 0.f;
-    } else {
-      for (int e = beg; e < end; e++) drows[(int64_t)e * lddr + c] = g * sc;
     }
   }
 }
@@ -1412,15 +1387,17 @@ extern "C" int rgnn_segment_reduce_bwd(const float* dM, int64_t lddm, const floa
   if (n == 0 || d == 0) return RGNN_OK;
   RGNN_CHECK_ARG(dM && rows && rowptr_t && d_rows, "null pointers");
   RGNN_CHECK_ARG(aggr >= 0 && aggr <= RGNN_AGGR_STD, "unknown aggregation");
-#define RGNN_SRBX(A) hipLaunchKernelGGL((k_segment_reduce_bwd_ext<A>), dim3(rgnn_blocks(n, 4)), dim3(256), 0, (hipStream_t)stream, dM, \
-                                        lddm, rows, ldr, rowptr_t, node_order, n, d, d_rows, lddr)
-  if (aggr == RGNN_AGGR_MIN) RGNN_SRBX(RGNN_AGGR_MIN);
-  else if (aggr == RGNN_AGGR_VAR) RGNN_SRBX(RGNN_AGGR_VAR);
-  else if (aggr == RGNN_AGGR_STD) RGNN_SRBX(RGNN_AGGR_STD);
-  else
-    hipLaunchKernelGGL(k_segment_reduce_bwd, dim3(rgnn_blocks(n, 4)), dim3(256), 0, (hipStream_t)stream, dM, lddm, rows, ldr,
-                       rowptr_t, node_order, n, d, aggr, d_rows, lddr);
-#undef RGNN_SRBX
+  switch (aggr) {                                         // the one place where the run-time code picks the instantiation
+#define RGNN_SRB(A)                                                                                                            \
+  case A:                                                                                                                      \
+    hipLaunchKernelGGL((k_segment_reduce_bwd<A>), dim3(rgnn_blocks(n, 4)), dim3(256), 0, (hipStream_t)stream, dM, lddm, rows, ldr, \
+                       rowptr_t, node_order, n, d, d_rows, lddr);                                                              \
+    break
+    RGNN_SRB(RGNN_AGGR_MAX); RGNN_SRB(RGNN_AGGR_MEAN); RGNN_SRB(RGNN_AGGR_ADD);
+    RGNN_SRB(RGNN_AGGR_MIN); RGNN_SRB(RGNN_AGGR_VAR); RGNN_SRB(RGNN_AGGR_STD);
+#undef RGNN_SRB
+    default: RGNN_CHECK_ARG(false, "unknown aggregation");
+  }
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
 }

@@ -41,7 +41,7 @@ struct MpParams {
   const float* We; int64_t ldwe;
   const float* ea; int de;
   const int32_t* rowptr; const int32_t* src; const int32_t* order;
-  int64_t n; int d; int aggr; int relu;
+  int64_t n; int d; int relu;
   float* out; int64_t ldo;
   int64_t chunk;  // nodes per wave (generic kernel)
   const int32_t* chunk_start; int n_chunks;  // work-balanced chunks (fast kernel); 1024 ticket ints follow the table
@@ -50,9 +50,99 @@ struct MpParams {
   float* out_absmax;                         // optional device word: atomic max of |out| over the rows written (f16x2 dense form)
 };
 
-// MODE 0: reduce into out[n, d];  MODE 1: store the per-edge hidden row (general pre_layers > 1 path)
-template <int VEC, int NCH, int DEP, int MODE>
+// ------------------------------------------------------------------------------------------------
+// What a schedule does with a message m_e = Q[s_e] + W_e a_e is a policy picked at compile time by the aggregation code of rgnn.h, or
+// by MP_EMIT: store the per-edge hidden row relu?(P[t] + b + m_e) instead of reducing (general pre_layers > 1 path).  The schedules
+// (k_mpnn, k_mpnn_fast, k_segment_reduce) have one body each; all that differs between the aggregations is in this struct.
+//   max | min : P + b + extremum_e(m_e) on targets with edges (the target term passes the maximum and the minimum)
+//   mean | add: P + b + sum_e(m_e) / cnt  |  cnt (P + b) + sum_e(m_e)
+//   var : mean_e(m_e^2) - (mean_e m_e)^2 is invariant under a shift of every m_e: the target term and the bias drop out, P and
+//         p_bias are not read.  The shift actually used is the segment's FIRST message q_0: the sums run over d_e = q_e - q_0,
+//         var = sum d^2 / cnt - (sum d / cnt)^2, so a single-edge segment and a segment of equal messages give exactly 0 and a
+//         common offset of the messages costs no digits (raw sums of q and q^2 cancel catastrophically there).  Not clamped.
+//   std : sqrt(relu(var) + 1e-5); var <= 0 (an empty segment too) gives the constant sqrt(1e-5), not 0.
+// An empty segment gives exactly 0 otherwise (torch-scatter), never the +-inf an extremum starts from.
+constexpr int MP_EMIT = RGNN_AGGR_STD + 1;
+constexpr float MP_STD_EPS = 1e-5f;
+template <int AGGR>
+struct MpReduce {
+  static constexpr bool moments = AGGR == RGNN_AGGR_VAR || AGGR == RGNN_AGGR_STD;
+  static constexpr bool emit = AGGR == MP_EMIT;
+  static constexpr bool reads_term = !moments;          // pn = p_bias + P[t]
+  // min | var | std track max |out| per lane (out_absmax, one atomic per wave); max | mean | add leave it to k_absmax_matrix
+  static constexpr bool tracks_absmax = AGGR == RGNN_AGGR_MIN || moments;
+  // k_mpnn reads the target term before a segment's edges, where the load overlaps the gather chain -- except min, whose
+  // <1, 1, 32> instance loses a wave per SIMD (81 VGPRs against 79) with the term live across the edge loop
+  static constexpr bool term_before_edges = AGGR != RGNN_AGGR_MIN;
+  // k_mpnn_fast, segment close.  Two properties of hipcc's code, each checked with -Rpass-analysis=kernel-resource-usage and the ISA
+  // of k_mpnn_fast<AGGR, 2, 8>; re-check both before changing either.
+  // mean: an fp32 division is ten instructions and five temporaries; with the four of a channel group interleaved <1, 2, 8> needs
+  //   36 bytes of scratch (the run-time-aggr kernel this replaced had 20), finished one after the other none.
+  static constexpr bool finish_in_turn = AGGR == RGNN_AGGR_MEAN;
+  // max | add | min: the count is wave-uniform -- a branch around the group's four values, as before the schedules were merged, not
+  //   four v_cndmask_b32 each (measured: no difference in time).  mean keeps the test inside finish(): hoisted it is back at 28 bytes.
+  static constexpr bool empty_by_branch = AGGR == RGNN_AGGR_MAX || AGGR == RGNN_AGGR_ADD || AGGR == RGNN_AGGR_MIN;
+  struct State { float s1, s2, q0; };                   // s1: extremum or sum; var / std: sum d, sum d^2 and q_0
+  static __device__ __forceinline__ State init() {
+    return {(AGGR == RGNN_AGGR_MAX) ? -INFINITY : (AGGR == RGNN_AGGR_MIN) ? INFINITY : 0.f, 0.f, 0.f};
+  }
+  // `first`: q opens its segment (var / std: it becomes q_0)
+  static __device__ __forceinline__ void step(State& s, float q, bool first) {
+    if (AGGR == RGNN_AGGR_MAX) s.s1 = fmaxf(s.s1, q);
+    else if (AGGR == RGNN_AGGR_MIN) s.s1 = fminf(s.s1, q);
+    else if (moments) {
+      if (first) s.q0 = q;
+      const float dd = q - s.q0;
+      s.s1 += dd;
+      s.s2 = __builtin_fmaf(dd, dd, s.s2);
+    } else s.s1 = s.s1 + q;
+  }
+  // the reduction of the messages alone
+  static __device__ __forceinline__ float reduced(const State& s, int cnt) {
+    if (cnt == 0) return (AGGR == RGNN_AGGR_STD) ? __builtin_sqrtf(MP_STD_EPS) : 0.f;
+    const float fc = (float)cnt;
+    if (AGGR == RGNN_AGGR_MEAN) return s.s1 / fc;
+    if (moments) {
+      const float mu = s.s1 / fc;
+      const float var = s.s2 / fc - mu * mu;
+      if (AGGR == RGNN_AGGR_VAR) return var;
+      return (var > 0.f) ? sqrtf(var + MP_STD_EPS) : __builtin_sqrtf(MP_STD_EPS);
+    }
+    return s.s1;
+  }
+  // ... and with the target term
+  static __device__ __forceinline__ float finish(const State& s, float pn, int cnt) {
+    const float r = reduced(s, cnt);
+    if (moments || cnt == 0) return r;
+    return (AGGR == RGNN_AGGR_ADD) ? (float)cnt * pn + r : pn + r;
+  }
+  static __device__ __forceinline__ float hidden(float pn, float q, int relu) {   // (emit)
+    const float x = pn + q;
+    return relu ? fmaxf(x, 0.f) : x;
+  }
+};
+
+template <int VEC, int NCH>
+__device__ __forceinline__ void mp_read_term(const float* p_bias, const float* P_row, const int (&ch)[NCH], const bool (&ok)[NCH],
+                                             float (&pn)[NCH][VEC]) {
+#pragma unroll
+  for (int t = 0; t < NCH; t++)
+    if (ok[t]) {
+#pragma unroll
+      for (int v = 0; v < VEC; v++) {
+        float x = p_bias ? p_bias[ch[t] + v] : 0.f;
+        if (P_row) x += P_row[ch[t] + v];
+        pn[t][v] = x;
+      }
+    }
+}
+
+// One wave per run of consecutive segments, VEC x NCH channels per lane and pass, the W_e slice of the lane's channels in registers,
+// indices and attributes wave-uniform: a chain of dependent loads per edge (four times the time of k_mpnn_fast on the C2 graph) that
+// takes any width, alignment and attribute count.
+template <int AGGR, int VEC, int NCH, int DEP>
 __global__ __launch_bounds__(MP_THREADS) void k_mpnn(const MpParams p) {
+  using R = MpReduce<AGGR>;
   const int lane = threadIdx.x & 63;
   // XCD-aware: consecutive chunks of nodes (hence frames) go to the same XCD (workgroup b runs on XCD b % 8)
   const int nb = gridDim.x;
@@ -65,6 +155,7 @@ __global__ __launch_bounds__(MP_THREADS) void k_mpnn(const MpParams p) {
   int64_t node_end = node_beg + p.chunk;
   if (node_end > p.n) node_end = p.n;
   if (node_beg >= p.n) return;
+  float amax = 0.f;
 
   constexpr int PASS = 64 * VEC * NCH;  // channels per pass
   for (int c0 = 0; c0 < p.d; c0 += PASS) {
@@ -85,27 +176,17 @@ __global__ __launch_bounds__(MP_THREADS) void k_mpnn(const MpParams p) {
     for (int64_t pos = node_beg; pos < node_end; pos++) {
       const int64_t node = p.order ? (int64_t)p.order[pos] : pos;
       const int beg = p.rowptr[pos], end = p.rowptr[pos + 1];  // CSR is laid out in visiting order
-      float acc[NCH][VEC];
+      typename R::State st[NCH][VEC];
       float pn[NCH][VEC];
 #pragma unroll
       for (int t = 0; t < NCH; t++)
 #pragma unroll
         for (int v = 0; v < VEC; v++) {
-          acc[t][v] = (p.aggr == RGNN_AGGR_MAX) ? -INFINITY : 0.f;
+          st[t][v] = R::init();
           pn[t][v] = 0.f;
         }
-      if (MODE == 1 || end > beg) {
-#pragma unroll
-        for (int t = 0; t < NCH; t++)
-          if (ok[t]) {
-#pragma unroll
-            for (int v = 0; v < VEC; v++) {
-              float x = p.p_bias ? p.p_bias[ch[t] + v] : 0.f;
-              if (p.P) x += p.P[node * p.ldp + ch[t] + v];
-              pn[t][v] = x;
-            }
-          }
-      }
+      // the target term of a segment with edges
+      if (R::reads_term && R::term_before_edges && end > beg) mp_read_term<VEC, NCH>(p.p_bias, p.P ? p.P + node * p.ldp : nullptr, ch, ok, pn);
       for (int e = beg; e < end; e++) {
         const int s = p.src[e];
         float a[DEP];
@@ -115,9 +196,9 @@ __global__ __launch_bounds__(MP_THREADS) void k_mpnn(const MpParams p) {
         for (int t = 0; t < NCH; t++) {
           if (!ok[t]) continue;
           float q[VEC];
-          if (VEC == 4) {
+          if constexpr (VEC == 4) {
             const float4 q4 = *(const float4*)(p.Q + (int64_t)s * p.ldq + ch[t]);
-            q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
+            q[0] = q4.x; q[1 % VEC] = q4.y; q[2 % VEC] = q4.z; q[3 % VEC] = q4.w;
           } else {
 #pragma unroll
             for (int v = 0; v < VEC; v++) q[v] = p.Q[(int64_t)s * p.ldq + ch[t] + v];
@@ -127,47 +208,36 @@ __global__ __launch_bounds__(MP_THREADS) void k_mpnn(const MpParams p) {
             float r = q[v];
 #pragma unroll
             for (int k = 0; k < DEP; k++) r = __builtin_fmaf(we[t][v][k], a[k], r);
-            q[v] = r;
-          }
-          if (MODE == 0) {
-#pragma unroll
-            for (int v = 0; v < VEC; v++)
-              acc[t][v] = (p.aggr == RGNN_AGGR_MAX) ? fmaxf(acc[t][v], q[v]) : acc[t][v] + q[v];
-          } else {
-            float* h = p.out + (int64_t)e * p.ldo + ch[t];
-#pragma unroll
-            for (int v = 0; v < VEC; v++) {
-              float x = pn[t][v] + q[v];
-              if (p.relu) x = fmaxf(x, 0.f);
-              h[v] = x;
-            }
+            if constexpr (R::emit) p.out[(int64_t)e * p.ldo + ch[t] + v] = R::hidden(pn[t][v], r, p.relu);
+            else R::step(st[t][v], r, e == beg);
           }
         }
       }
-      if (MODE == 0) {
+      if constexpr (!R::emit) {
         const int cnt = end - beg;
+        if (R::reads_term && !R::term_before_edges && cnt > 0) mp_read_term<VEC, NCH>(p.p_bias, p.P ? p.P + node * p.ldp : nullptr, ch, ok, pn);
 #pragma unroll
         for (int t = 0; t < NCH; t++) {
           if (!ok[t]) continue;
           float o[VEC];
 #pragma unroll
           for (int v = 0; v < VEC; v++) {
-            float x = 0.f;  // empty segment -> exactly 0 (torch-scatter)
-            if (cnt > 0) {
-              if (p.aggr == RGNN_AGGR_MAX) x = pn[t][v] + acc[t][v];
-              else if (p.aggr == RGNN_AGGR_MEAN) x = pn[t][v] + acc[t][v] / (float)cnt;
-              else x = (float)cnt * pn[t][v] + acc[t][v];
-            }
-            o[v] = x;
+            o[v] = R::finish(st[t][v], pn[t][v], cnt);
+            if (R::tracks_absmax) amax = fmaxf(amax, fabsf(o[v]));
           }
           float* dst = p.out + node * p.ldo + ch[t];
-          if (VEC == 4) *(float4*)dst = make_float4(o[0], o[1], o[2], o[3]);
+          if constexpr (VEC == 4) *(float4*)dst = make_float4(o[0], o[1 % VEC], o[2 % VEC], o[3 % VEC]);
           else
 #pragma unroll
             for (int v = 0; v < VEC; v++) dst[v] = o[v];
         }
       }
     }
+  }
+  if (R::tracks_absmax && p.out_absmax) {                // one atomic per wave, spread over the slots of the bound (rgnn.h)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    if (lane == 0) atomicMax((unsigned int*)p.out_absmax + (gw & (RGNN_BOUND_SLOTS - 1)), __float_as_uint(amax));
   }
 }
 
@@ -182,9 +252,10 @@ __global__ __launch_bounds__(MP_THREADS) void k_mpnn(const MpParams p) {
 //     lane l holds a[l / DEP][l % DEP]) and broadcasts them with v_readlane -> no dependent scalar loads;
 //   * software-pipelines the row gathers two edges ahead (4 rows in flight per wave);
 //   * visits the targets in `order` (grid-cell order): neighbouring targets share sources -> the gathers hit L2.
+// Registers per channel group: 4 DEP (W_e) + 16 (rows in flight) + 4 (q) + the policy's state (4; var / std 12) + 4 (target term).
 // ------------------------------------------------------------------------------------------------
 // (at least 3 waves per SIMD: the D = 464 instance wants 175 VGPRs, seven more than three resident waves leave it)
-template <int NCH, int DEP, int MODE>
+template <int AGGR, int NCH, int DEP>
 __global__ __launch_bounds__(MP_THREADS) __attribute__((amdgpu_waves_per_eu(3))) void k_mpnn_fast(const float* __restrict__ P, int64_t ldp,
                                                          const float* __restrict__ p_bias,
                                                          const float* __restrict__ Q, int64_t ldq,
@@ -194,8 +265,10 @@ __global__ __launch_bounds__(MP_THREADS) __attribute__((amdgpu_waves_per_eu(3)))
                                                          const int32_t* __restrict__ src,
                                                          const int32_t* __restrict__ order,
                                                          const int32_t* __restrict__ chunk_start, int n_chunks,
-                                                         int32_t* __restrict__ queue, int64_t n, int d, int aggr,
-                                                         int relu, float* __restrict__ out, int64_t ldo) {
+                                                         int32_t* __restrict__ queue, int64_t n, int d, int relu,
+                                                         float* __restrict__ out, int64_t ldo,
+                                                         float* __restrict__ out_absmax) {
+  using R = MpReduce<AGGR>;
   constexpr int EPL = 64 / DEP;  // edges whose attributes fit one 64-lane load
   const int lane = threadIdx.x & 63;
   // Persistent waves pull chunks from a per-XCD ticket counter: XCD x (= workgroup id % 8, observed placement) owns the
@@ -225,6 +298,7 @@ __global__ __launch_bounds__(MP_THREADS) __attribute__((amdgpu_waves_per_eu(3)))
     }
   }
   const int ea_edge = lane / DEP, ea_k = lane % DEP;  // which attribute this lane fetches in an attribute block
+  float amax = 0.f;
 
   for (;;) {
     int cidx = 0;
@@ -250,17 +324,20 @@ __global__ __launch_bounds__(MP_THREADS) __attribute__((amdgpu_waves_per_eu(3)))
 
     // node cursor (all wave-uniform)
     int ni = 0, node = 0, node_end = 0, cnt = 0;
-    float4 pn[NCH], acc[NCH];
-    const float init = (aggr == RGNN_AGGR_MAX) ? -INFINITY : 0.f;
+    bool first = true;                                 // the next edge opens its segment
+    float4 pn[NCH];
+    typename R::State st[NCH][4];
     auto open_node = [&](int i) {
       node = __builtin_amdgcn_readlane(my_node, i);
       node_end = __builtin_amdgcn_readlane(my_rp, i + 1);
       cnt = node_end - __builtin_amdgcn_readlane(my_rp, i);
+      first = true;
   #pragma unroll
       for (int t = 0; t < NCH; t++) {
-        acc[t] = make_float4(init, init, init, init);
+  #pragma unroll
+        for (int v = 0; v < 4; v++) st[t][v] = R::init();
         pn[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (cnt > 0) {
+        if (R::reads_term && cnt > 0) {
           if (p_bias) pn[t] = *(const float4*)(p_bias + ch[t]);
           if (P) {
             const float4 x = *(const float4*)(P + (int64_t)node * ldp + ch[t]);
@@ -270,22 +347,23 @@ __global__ __launch_bounds__(MP_THREADS) __attribute__((amdgpu_waves_per_eu(3)))
       }
     };
     auto close_node = [&]() {
-      if (MODE != 0) return;
-      const float fc = (float)cnt;
+      if (R::emit) return;
   #pragma unroll
       for (int t = 0; t < NCH; t++) {
         if (!ok[t]) continue;
-        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);  // empty segment -> exactly 0 (torch-scatter)
-        if (cnt > 0) {
-          if (aggr == RGNN_AGGR_MAX)
-            o = make_float4(pn[t].x + acc[t].x, pn[t].y + acc[t].y, pn[t].z + acc[t].z, pn[t].w + acc[t].w);
-          else if (aggr == RGNN_AGGR_MEAN)
-            o = make_float4(pn[t].x + acc[t].x / fc, pn[t].y + acc[t].y / fc, pn[t].z + acc[t].z / fc,
-                            pn[t].w + acc[t].w / fc);
-          else
-            o = make_float4(fc * pn[t].x + acc[t].x, fc * pn[t].y + acc[t].y, fc * pn[t].z + acc[t].z,
-                            fc * pn[t].w + acc[t].w);
+        const float pv[4] = {pn[t].x, pn[t].y, pn[t].z, pn[t].w};
+        float ov[4] = {0.f, 0.f, 0.f, 0.f};
+        if (!R::empty_by_branch || cnt > 0) {
+          if (R::empty_by_branch) asm volatile("");      // (nothing to speculate: hipcc keeps the branch)
+  #pragma unroll
+          for (int v = 0; v < 4; v++) {
+            ov[v] = R::finish(st[t][v], pv[v], cnt);
+            // finish_in_turn: value v + 1 becomes available when value v is done (see MpReduce)
+            if (R::finish_in_turn && v < 3) asm volatile("" : "+v"(ov[v]), "+v"(st[t][v + 1].s1));
+          }
         }
+        const float4 o = make_float4(ov[0], ov[1], ov[2], ov[3]);
+        if (R::tracks_absmax) amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
         *(float4*)(out + (int64_t)node * ldo + ch[t]) = o;
       }
     };
@@ -341,19 +419,16 @@ __global__ __launch_bounds__(MP_THREADS) __attribute__((amdgpu_waves_per_eu(3)))
           }
   #pragma unroll
           for (int t = 0; t < NCH; t++) {
-            if (MODE == 0) {
-              if (aggr == RGNN_AGGR_MAX) {
-                acc[t].x = fmaxf(acc[t].x, q[t].x); acc[t].y = fmaxf(acc[t].y, q[t].y);
-                acc[t].z = fmaxf(acc[t].z, q[t].z); acc[t].w = fmaxf(acc[t].w, q[t].w);
-              } else {
-                acc[t].x += q[t].x; acc[t].y += q[t].y; acc[t].z += q[t].z; acc[t].w += q[t].w;
-              }
-            } else if (ok[t]) {
-              float4 h = make_float4(pn[t].x + q[t].x, pn[t].y + q[t].y, pn[t].z + q[t].z, pn[t].w + q[t].w);
-              if (relu) { h.x = fmaxf(h.x, 0.f); h.y = fmaxf(h.y, 0.f); h.z = fmaxf(h.z, 0.f); h.w = fmaxf(h.w, 0.f); }
-              *(float4*)(out + (int64_t)e * ldo + ch[t]) = h;
+            if constexpr (R::emit) {
+              if (ok[t])
+                *(float4*)(out + (int64_t)e * ldo + ch[t]) = make_float4(R::hidden(pn[t].x, q[t].x, relu), R::hidden(pn[t].y, q[t].y, relu),
+                                                                         R::hidden(pn[t].z, q[t].z, relu), R::hidden(pn[t].w, q[t].w, relu));
+            } else {
+              R::step(st[t][0], q[t].x, first); R::step(st[t][1], q[t].y, first);
+              R::step(st[t][2], q[t].z, first); R::step(st[t][3], q[t].w, first);
             }
           }
+          first = false;
         }
   #pragma unroll
         for (int t = 0; t < NCH; t++) { qa[t] = qc[t]; qb[t] = qd[t]; }
@@ -367,6 +442,176 @@ __global__ __launch_bounds__(MP_THREADS) __attribute__((amdgpu_waves_per_eu(3)))
       if (++ni >= cn) break;
       open_node(ni);
     }
+  }
+  if (R::tracks_absmax && out_absmax) {                  // one atomic per wave, spread over the slots of the bound (rgnn.h)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    if (lane == 0)
+      atomicMax((unsigned int*)out_absmax + (((blockIdx.y * gridDim.x + blockIdx.x) * MP_WAVES + (threadIdx.x >> 6)) & (RGNN_BOUND_SLOTS - 1)),
+                __float_as_uint(amax));
+  }
+}
+
+// min past 256 channels (two channel groups per lane, 5 .. 8 attributes) keeps the body it had before the schedules were merged:
+// k_mpnn_fast<MIN, 2, 8> compiles to the same registers and the same arithmetic per edge, yet measures 1.5 - 2 % slower on the C2
+// graph at 464 channels (MEASUREMENTS.md 4.2; neither the selects at the segment close nor the s_nop after the lane reads are the
+// cause, both were taken out and measured).  The only instantiation launched is <2, 8>; it goes when the shared body is level.  A fix
+// to the ticket loop or the two-edge pipeline of k_mpnn_fast has to be made here as well.
+template <int NCH, int DEP>
+__global__ __launch_bounds__(MP_THREADS) __attribute__((amdgpu_waves_per_eu(3))) void k_mpnn_fast_min(
+    const float* __restrict__ P, int64_t ldp, const float* __restrict__ p_bias, const float* __restrict__ Q, int64_t ldq,
+    const float* __restrict__ We, int64_t ldwe, const float* __restrict__ ea, int de, const int32_t* __restrict__ rowptr,
+    const int32_t* __restrict__ src, const int32_t* __restrict__ order, const int32_t* __restrict__ chunk_start, int n_chunks,
+    int32_t* __restrict__ queue, int64_t n, int d, float* __restrict__ out, int64_t ldo, float* __restrict__ out_absmax) {
+  constexpr int EPL = 64 / DEP;  // edges whose attributes fit one 64-lane load
+  const int lane = threadIdx.x & 63;
+  const int xcd = blockIdx.x & 7;
+  const int c_lo = (int)((int64_t)n_chunks * xcd / 8), c_hi = (int)((int64_t)n_chunks * (xcd + 1) / 8);
+  int32_t* ticket = queue + (blockIdx.y * 8 + xcd) * 16;  // one counter per (channel block, XCD), 64 B apart
+
+  int ch[NCH];
+  bool ok[NCH];
+  float4 we[NCH][DEP];
+#pragma unroll
+  for (int t = 0; t < NCH; t++) {
+    const int c = (blockIdx.y * NCH + t) * 256 + lane * 4;
+    ok[t] = c < d;
+    ch[t] = ok[t] ? c : 0;
+#pragma unroll
+    for (int k = 0; k < DEP; k++) {
+      const bool kk = ok[t] && k < de;
+      we[t][k].x = kk ? We[(int64_t)(ch[t] + 0) * ldwe + k] : 0.f;
+      we[t][k].y = kk ? We[(int64_t)(ch[t] + 1) * ldwe + k] : 0.f;
+      we[t][k].z = kk ? We[(int64_t)(ch[t] + 2) * ldwe + k] : 0.f;
+      we[t][k].w = kk ? We[(int64_t)(ch[t] + 3) * ldwe + k] : 0.f;
+    }
+  }
+  const int ea_edge = lane / DEP, ea_k = lane % DEP;  // which attribute this lane fetches in an attribute block
+  float amax = 0.f;
+
+  for (;;) {
+    int cidx = 0;
+    if (lane == 0) cidx = c_lo + atomicAdd(ticket, 1);
+    cidx = __builtin_amdgcn_readfirstlane(cidx);
+    if (cidx >= c_hi) {
+      if (lane == 0) {                                   // the last wave of a queue to run dry puts both counters back to zero
+        const int waves = (int)(gridDim.x >> 3) * MP_WAVES;
+        if (atomicAdd(ticket + 1, 1) == waves - 1) { ticket[0] = 0; ticket[1] = 0; }
+      }
+      break;
+    }
+    const int pos_beg = __builtin_amdgcn_readfirstlane(chunk_start[cidx]);
+    const int cn = __builtin_amdgcn_readfirstlane(chunk_start[cidx + 1]) - pos_beg;  // targets of this chunk (<= 63)
+    if (cn <= 0) continue;
+    const int my_rp = rowptr[pos_beg + min(lane, cn)];
+    const int my_node = order ? order[pos_beg + min(lane, cn - 1)] : (pos_beg + min(lane, cn - 1));
+    const int e_lo = __builtin_amdgcn_readlane(my_rp, 0);
+    const int e_hi = __builtin_amdgcn_readlane(my_rp, cn);
+
+    int ni = 0, node = 0, node_end = 0, cnt = 0;       // target cursor (all wave-uniform)
+    float4 s1[NCH], q0[NCH];                           // s1 = running minimum, q0 = target term
+    auto open_node = [&](int i) {
+      node = __builtin_amdgcn_readlane(my_node, i);
+      node_end = __builtin_amdgcn_readlane(my_rp, i + 1);
+      cnt = node_end - __builtin_amdgcn_readlane(my_rp, i);
+#pragma unroll
+      for (int t = 0; t < NCH; t++) {
+        s1[t] = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
+        q0[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (cnt > 0) {
+          if (p_bias) q0[t] = *(const float4*)(p_bias + ch[t]);
+          if (P) {
+            const float4 x = *(const float4*)(P + (int64_t)node * ldp + ch[t]);
+            q0[t].x += x.x; q0[t].y += x.y; q0[t].z += x.z; q0[t].w += x.w;
+          }
+        }
+      }
+    };
+    auto close_node = [&]() {
+#pragma unroll
+      for (int t = 0; t < NCH; t++) {
+        if (!ok[t]) continue;
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);     // empty segment -> exactly 0 (torch-scatter), not +inf
+        if (cnt > 0) o = make_float4(q0[t].x + s1[t].x, q0[t].y + s1[t].y, q0[t].z + s1[t].z, q0[t].w + s1[t].w);
+        amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+        *(float4*)(out + (int64_t)node * ldo + ch[t]) = o;
+      }
+    };
+    open_node(0);
+
+    // flat edge stream [e_lo, e_hi): 64 indices per coalesced load, row gathers two edges ahead, across node borders
+    int src_cur = (e_lo + lane < e_hi) ? src[e_lo + lane] : 0;
+    float4 qa[NCH], qb[NCH];
+    float my_ea = 0.f;
+    for (int eb = e_lo; eb < e_hi; eb += 64) {
+      const int src_nxt = (eb + 64 + lane < e_hi) ? src[eb + 64 + lane] : 0;
+      auto row_of = [&](int j, float4* q) {  // Q row of edge eb + j (clamped to the stream; surplus gathers are discarded)
+        const int jj = min(j, e_hi - 1 - eb);
+        const int s = (jj < 64) ? __builtin_amdgcn_readlane(src_cur, jj) : __builtin_amdgcn_readlane(src_nxt, jj - 64);
+#pragma unroll
+        for (int t = 0; t < NCH; t++) q[t] = *(const float4*)(Q + (int64_t)s * ldq + ch[t]);
+      };
+      auto attr_block = [&](int blk) {  // attributes of edges eb + [blk*EPL, blk*EPL+EPL), one value per lane
+        const int e = eb + blk * EPL + ea_edge;
+        return (e < e_hi && ea_k < de) ? ea[(int64_t)e * de + ea_k] : 0.f;
+      };
+      if (eb == e_lo) {
+        row_of(0, qa); row_of(1, qb);
+        my_ea = attr_block(0);
+      }
+      const int nbk = min(64, e_hi - eb);
+      for (int j = 0; j < nbk; j += 2) {
+        float4 qc[NCH], qd[NCH];
+        row_of(j + 2, qc); row_of(j + 3, qd);
+        float ea_next = my_ea;
+        if (((j + 2) % EPL) == 0) ea_next = attr_block((j + 2) / EPL);
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+          const int e = eb + j + u;
+          if (e >= e_hi) break;
+          while (e >= node_end) {  // crossed into the next target (possibly over empty ones)
+            close_node();
+            ni++;
+            open_node(ni);
+          }
+          float4 q[NCH];
+#pragma unroll
+          for (int t = 0; t < NCH; t++) q[t] = (u == 0) ? qa[t] : qb[t];
+          const int lane0 = ((j + u) % EPL) * DEP;
+#pragma unroll
+          for (int k = 0; k < DEP; k++) {
+            const float ak = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_ea), lane0 + k));
+#pragma unroll
+            for (int t = 0; t < NCH; t++) {
+              q[t].x = __builtin_fmaf(we[t][k].x, ak, q[t].x); q[t].y = __builtin_fmaf(we[t][k].y, ak, q[t].y);
+              q[t].z = __builtin_fmaf(we[t][k].z, ak, q[t].z); q[t].w = __builtin_fmaf(we[t][k].w, ak, q[t].w);
+            }
+          }
+#pragma unroll
+          for (int t = 0; t < NCH; t++) {
+            s1[t].x = fminf(s1[t].x, q[t].x); s1[t].y = fminf(s1[t].y, q[t].y);
+            s1[t].z = fminf(s1[t].z, q[t].z); s1[t].w = fminf(s1[t].w, q[t].w);
+          }
+        }
+#pragma unroll
+        for (int t = 0; t < NCH; t++) { qa[t] = qc[t]; qb[t] = qd[t]; }
+        my_ea = ea_next;
+      }
+      src_cur = src_nxt;
+    }
+    // the target that was open when the stream ended, then any trailing targets without edges
+    for (;;) {
+      close_node();
+      if (++ni >= cn) break;
+      open_node(ni);
+    }
+  }
+  if (out_absmax) {                                    // one atomic per wave, spread over the slots of the bound (rgnn.h)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    if (lane == 0)
+      atomicMax((unsigned int*)out_absmax + (((blockIdx.y * gridDim.x + blockIdx.x) * MP_WAVES + (threadIdx.x >> 6)) & (RGNN_BOUND_SLOTS - 1)),
+                __float_as_uint(amax));
   }
 }
 
@@ -625,27 +870,36 @@ __global__ __launch_bounds__(256) void k_partition(const int32_t* __restrict__ r
   chunk_start[c] = (int32_t)lo;
 }
 
-template <int MODE>
+// -> 0: the launch wrote every row; 1: k_mpnn_max took it (the kernel that can record the winners); 2: every row, and the kernel
+// tracked |out| itself (k_mpnn_max with out_absmax, and codes 3 - 5).  What differs between the aggregations here is launch geometry.
+template <int AGGR>
 int dispatch(MpParams& p, hipStream_t s) {
-  const bool vec4 = (p.d % 4 == 0) && (p.ldq % 4 == 0) && (p.ldo % 4 == 0) && (((uintptr_t)p.Q & 15) == 0) &&
-                    (((uintptr_t)p.out & 15) == 0) && (p.P == nullptr || ((p.ldp % 4 == 0) && (((uintptr_t)p.P & 15) == 0))) &&
-                    (p.p_bias == nullptr || (((uintptr_t)p.p_bias & 15) == 0));
-  if (vec4 && p.chunk_start != nullptr) {
-    const int nch = (p.de <= 8 && p.d > 256 && RGNN_ENV("RGNN_MPNN_NCH1") == nullptr) ? 2 : 1;  // 64 weight registers either way
+  using R = MpReduce<AGGR>;
+  constexpr bool ext = R::tracks_absmax;                // codes 3 - 5
+  const bool rows16 = (p.d % 4 == 0) && (p.ldq % 4 == 0) && (p.ldo % 4 == 0) && (((uintptr_t)p.Q & 15) == 0) &&
+                      (((uintptr_t)p.out & 15) == 0);
+  const bool term16 = !R::reads_term || ((p.P == nullptr || ((p.ldp % 4 == 0) && (((uintptr_t)p.P & 15) == 0))) &&
+                                         (p.p_bias == nullptr || (((uintptr_t)p.p_bias & 15) == 0)));
+  // two channel groups per lane past 256 channels while the weights stay within 64 registers -- except var / std with 5 .. 8
+  // attributes: q_0 and two sums per group next to 64 weight registers spill under three waves per SIMD (56 / 64 bytes of scratch):
+  // one group, twice the blocks in y
+  const int nch = (p.d > 256 && p.de <= (R::moments ? 4 : 8)) ? 2 : 1;
+  // (RGNN_MPNN_QUEUE_INTS holds the ticket counters of 8 channel blocks: wider messages of codes 3 - 5 stay on k_mpnn)
+  const bool queues_fit = !ext || p.d <= 8 * 256 * ((AGGR == RGNN_AGGR_MIN || p.de <= 4) ? 2 : 1);
+  if (rows16 && term16 && queues_fit && p.chunk_start != nullptr && p.de <= (ext ? 8 : 32)) {
     const unsigned ny = (unsigned)((p.d + 256 * nch - 1) / (256 * nch));
     int64_t blocks = (p.n_chunks + MP_WAVES - 1) / MP_WAVES;
-    static const int per_cu = RGNN_ENV("RGNN_MPNN_WG_PER_CU") ? atoi(RGNN_ENV("RGNN_MPNN_WG_PER_CU")) : 3;
-    if (blocks > 256 * per_cu) blocks = 256 * per_cu;  // persistent: 3 workgroups of 4 waves per CU
+    if (blocks > 256 * 3) blocks = 256 * 3;  // persistent: 3 workgroups of 4 waves per CU
     blocks = (blocks + 7) / 8 * 8;
     const dim3 grid((unsigned)blocks, ny), block(MP_THREADS);
     // ticket counters live behind the chunk table: zeroed by rgnn_mpnn_partition, and every launch leaves them zero again
     // (the last wave of a queue to run dry resets it) -- a memset per launch was three fill kernels (unaligned head /
     // body / tail), 15 us per layer
     int32_t* queue = const_cast<int32_t*>(p.chunk_start) + p.n_chunks + 1;
-    // max aggregation without per-target rows: k_mpnn_max
-    const int64_t q_bytes = ((p.n - 1) * p.ldq + p.d) * 4;   // (sources are node ids < n)
-    if (MODE == 0 && p.aggr == RGNN_AGGR_MAX && p.P == nullptr && p.de <= 8 && q_bytes < ((int64_t)1 << 31) &&
-        RGNN_ENV("RGNN_MPNN_NOSPEC") == nullptr) {
+    if constexpr (AGGR == RGNN_AGGR_MAX) {
+      // max aggregation without per-target rows: k_mpnn_max
+      const int64_t q_bytes = ((p.n - 1) * p.ldq + p.d) * 4;   // (sources are node ids < n)
+      if (p.P == nullptr && p.de <= 8 && q_bytes < ((int64_t)1 << 31)) {
 #define RGNN_MPX(NCH, DEP)                                                                                          \
   do {                                                                                                              \
     if (p.arg_out && p.out_absmax)                                                                                  \
@@ -661,25 +915,36 @@ int dispatch(MpParams& p, hipStream_t s) {
       hipLaunchKernelGGL((k_mpnn_max<NCH, DEP, false>), grid, block, 0, s, p.p_bias, p.Q, p.ldq, p.We, p.ldwe, p.ea, p.de, p.rowptr, \
                          p.src, p.order, p.chunk_start, p.n_chunks, queue, p.n, p.d, p.out, p.ldo, (int)q_bytes, p.skip_empty, nullptr); \
   } while (0)
-      if (nch == 2) { if (p.de <= 4) RGNN_MPX(2, 4); else RGNN_MPX(2, 8); }
-      else if (p.de <= 4) RGNN_MPX(1, 4);
-      else RGNN_MPX(1, 8);
+        if (nch == 2) { if (p.de <= 4) RGNN_MPX(2, 4); else RGNN_MPX(2, 8); }
+        else if (p.de <= 4) RGNN_MPX(1, 4);
+        else RGNN_MPX(1, 8);
 #undef RGNN_MPX
-      return p.out_absmax ? 2 : 1;                      // (the kernel that can record the winners; 2: it tracked |out| as well)
+        return p.out_absmax ? 2 : 1;
+      }
     }
-#define RGNN_MPF(NCH, DEP)                                                                                          \
-  hipLaunchKernelGGL((k_mpnn_fast<NCH, DEP, MODE>), grid, block, 0, s, p.P, p.ldp, p.p_bias, p.Q, p.ldq, p.We, p.ldwe,   \
-                     p.ea, p.de, p.rowptr, p.src, p.order, p.chunk_start, p.n_chunks, queue, p.n, p.d, p.aggr, p.relu,   \
-                     p.out, p.ldo)
-    if (nch == 2) { if (p.de <= 4) RGNN_MPF(2, 4); else RGNN_MPF(2, 8); }
-    else if (p.de <= 4) RGNN_MPF(1, 4);
+#define RGNN_MPF(NCH, DEP)                                                                                               \
+  hipLaunchKernelGGL((k_mpnn_fast<AGGR, NCH, DEP>), grid, block, 0, s, p.P, p.ldp, p.p_bias, p.Q, p.ldq, p.We, p.ldwe, p.ea,  \
+                     p.de, p.rowptr, p.src, p.order, p.chunk_start, p.n_chunks, queue, p.n, p.d, p.relu, p.out, p.ldo,       \
+                     p.out_absmax)
+    if (nch == 2) {
+      if (p.de <= 4) RGNN_MPF(2, 4);
+      else if constexpr (AGGR == RGNN_AGGR_MIN)          // (see k_mpnn_fast_min)
+        hipLaunchKernelGGL((k_mpnn_fast_min<2, 8>), grid, block, 0, s, p.P, p.ldp, p.p_bias, p.Q, p.ldq, p.We, p.ldwe, p.ea, p.de,
+                           p.rowptr, p.src, p.order, p.chunk_start, p.n_chunks, queue, p.n, p.d, p.out, p.ldo, p.out_absmax);
+      else if constexpr (!R::moments) RGNN_MPF(2, 8);
+    } else if (p.de <= 4) RGNN_MPF(1, 4);
     else if (p.de <= 8) RGNN_MPF(1, 8);
-    else if (p.de <= 16) RGNN_MPF(1, 16);
-    else RGNN_MPF(1, 32);
+    else if constexpr (!ext) {
+      if (p.de <= 16) RGNN_MPF(1, 16);
+      else RGNN_MPF(1, 32);
+    }
 #undef RGNN_MPF
-    return 0;
+    return ext ? 2 : 0;
   }
-  // generic path: one wave per chunk, W_e slice in registers, scalar channels
+  // generic path: one wave per chunk of segments.  max | mean | add | emit: scalar channels, two groups per lane; min | var | std: one
+  // group of four channels where the rows allow 16-byte accesses and the attributes fit 8 registers per channel, else one channel
+  constexpr int NCH = ext ? 1 : 2;
+  const bool vec4 = ext && rows16 && p.de <= 8;
   const int64_t target_waves = 256 * 16;
   int64_t chunk = (p.n + target_waves - 1) / target_waves;
   if (chunk < 8) chunk = 8;
@@ -688,406 +953,45 @@ int dispatch(MpParams& p, hipStream_t s) {
   int64_t blocks = (waves + MP_WAVES - 1) / MP_WAVES;
   blocks = (blocks + 7) / 8 * 8;
   const dim3 grid((unsigned)blocks), block(MP_THREADS);
-#define RGNN_MP_LAUNCH(VEC, NCH, DEP) hipLaunchKernelGGL((k_mpnn<VEC, NCH, DEP, MODE>), grid, block, 0, s, p)
-  if (p.de <= 4) RGNN_MP_LAUNCH(1, 2, 4);
-  else if (p.de <= 16) RGNN_MP_LAUNCH(1, 2, 16);
-  else RGNN_MP_LAUNCH(1, 2, 32);
+#define RGNN_MP_LAUNCH(VEC, NCH, DEP) hipLaunchKernelGGL((k_mpnn<AGGR, VEC, NCH, DEP>), grid, block, 0, s, p)
+  if (vec4) {
+    if constexpr (ext) { if (p.de <= 4) RGNN_MP_LAUNCH(4, 1, 4); else RGNN_MP_LAUNCH(4, 1, 8); }
+  } else if (p.de <= 4) RGNN_MP_LAUNCH(1, NCH, 4);
+  else if (p.de <= 16) RGNN_MP_LAUNCH(1, NCH, 16);
+  else RGNN_MP_LAUNCH(1, NCH, 32);
 #undef RGNN_MP_LAUNCH
-  return 0;
+  return ext ? 2 : 0;
 }
 
-// rows [E, d] in CSR order -> out [n, d]
+// the one place where the run-time aggregation code picks the instantiation
+int dispatch_aggr(int aggr, MpParams& p, hipStream_t s) {
+  switch (aggr) {
+    case RGNN_AGGR_MAX: return dispatch<RGNN_AGGR_MAX>(p, s);
+    case RGNN_AGGR_MEAN: return dispatch<RGNN_AGGR_MEAN>(p, s);
+    case RGNN_AGGR_ADD: return dispatch<RGNN_AGGR_ADD>(p, s);
+    case RGNN_AGGR_MIN: return dispatch<RGNN_AGGR_MIN>(p, s);
+    case RGNN_AGGR_VAR: return dispatch<RGNN_AGGR_VAR>(p, s);
+    case RGNN_AGGR_STD: return dispatch<RGNN_AGGR_STD>(p, s);
+    default: return -1;                                  // (no such aggregation: nothing launched)
+  }
+}
+
+// rows [E, d] in CSR order -> out [n, d]: the reductions literally over the rows (no target term here)
+template <int AGGR>
 __global__ __launch_bounds__(256) void k_segment_reduce(const float* __restrict__ rows, int64_t ldr,
                                                        const int32_t* __restrict__ rowptr,
-                                                       const int32_t* __restrict__ order, int64_t n, int d, int aggr,
+                                                       const int32_t* __restrict__ order, int64_t n, int d,
                                                        float* __restrict__ out, int64_t ldo) {
+  using R = MpReduce<AGGR>;
   const int lane = threadIdx.x & 63;
   const int64_t pos = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (pos >= n) return;
   const int64_t node = order ? (int64_t)order[pos] : pos;
   const int beg = rowptr[pos], end = rowptr[pos + 1];
   for (int c = lane; c < d; c += 64) {
-    float acc = (aggr == RGNN_AGGR_MAX) ? -INFINITY : 0.f;
-    for (int e = beg; e < end; e++) {
-      const float v = rows[(int64_t)e * ldr + c];
-      acc = (aggr == RGNN_AGGR_MAX) ? fmaxf(acc, v) : acc + v;
-    }
-    float x = 0.f;
-    if (end > beg) x = (aggr == RGNN_AGGR_MEAN) ? acc / (float)(end - beg) : acc;
-    out[node * ldo + c] = x;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// min | var | std (codes 3 - 5), the aggregation a compile-time parameter; the kernels above keep serving codes 0 - 2.
-//   min : P + b + min_e(Q[s_e] + W_e a_e) on targets with edges (the target term passes the minimum as it passes the maximum)
-//   var : mean_e(m_e^2) - (mean_e m_e)^2 is invariant under a shift of every m_e: the target term and the bias drop out, P and
-//         p_bias are not read.  The shift actually used is the segment's FIRST message q_0: the sums run over d_e = q_e - q_0,
-//         var = sum d^2 / cnt - (sum d / cnt)^2, so a single-edge segment and a segment of equal messages give exactly 0 and a
-//         common offset of the messages costs no digits (raw sums of q and q^2 cancel catastrophically there).  Not clamped.
-//   std : sqrt(relu(var) + 1e-5); var <= 0 (an empty segment too) gives the constant sqrt(1e-5), not 0.
-// Work decomposition of k_mpnn (one wave per run of consecutive segments, lanes across channels, the W_e slice of the lane's
-// channels in registers, indices and attributes wave-uniform), one channel group per lane and pass: the var / std form holds
-// q_0 and two sums per channel, VEC (W_e) + 3 VEC + VEC (row) registers at DEP = 8 -- no scratch (MEASUREMENTS.md 4.2).
-// |out| is tracked per lane (out_absmax), one atomic per wave.
-constexpr float MP_STD_EPS = 1e-5f;
-template <int AGGR>
-__device__ __forceinline__ float mp_ext_finish(float s1, float s2, int cnt) {
-  // (AGGR 4 / 5) s1 = sum d, s2 = sum d^2 over the segment
-  if (cnt == 0) return (AGGR == RGNN_AGGR_STD) ? __builtin_sqrtf(MP_STD_EPS) : 0.f;
-  const float fc = (float)cnt;
-  const float mu = s1 / fc;
-  const float var = s2 / fc - mu * mu;
-  if (AGGR == RGNN_AGGR_VAR) return var;
-  return (var > 0.f) ? sqrtf(var + MP_STD_EPS) : __builtin_sqrtf(MP_STD_EPS);
-}
-
-template <int AGGR, int VEC, int DEP>
-__global__ __launch_bounds__(MP_THREADS) void k_mpnn_ext(const MpParams p) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t gw = (int64_t)blockIdx.x * MP_WAVES + wave;
-  const int64_t node_beg = gw * p.chunk;
-  int64_t node_end = node_beg + p.chunk;
-  if (node_end > p.n) node_end = p.n;
-  float amax = 0.f;
-  constexpr int PASS = 64 * VEC;
-  if (node_beg < p.n) {
-    for (int c0 = 0; c0 < p.d; c0 += PASS) {
-      const int ch = c0 + lane * VEC;
-      const bool ok = ch < p.d;                        // (VEC == 4: d % 4 == 0 is guaranteed by the dispatcher)
-      float we[VEC][DEP];
-#pragma unroll
-      for (int v = 0; v < VEC; v++)
-#pragma unroll
-        for (int k = 0; k < DEP; k++) we[v][k] = (ok && k < p.de) ? p.We[(int64_t)(ch + v) * p.ldwe + k] : 0.f;
-      for (int64_t pos = node_beg; pos < node_end; pos++) {
-        const int64_t node = p.order ? (int64_t)p.order[pos] : pos;
-        const int beg = p.rowptr[pos], end = p.rowptr[pos + 1];
-        float s1[VEC], s2[VEC], q0[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; v++) {
-          s1[v] = (AGGR == RGNN_AGGR_MIN) ? INFINITY : 0.f;
-          s2[v] = 0.f;
-          q0[v] = 0.f;
-        }
-        for (int e = beg; e < end; e++) {
-          const int s = p.src[e];
-          float a[DEP];
-#pragma unroll
-          for (int k = 0; k < DEP; k++) a[k] = (k < p.de) ? p.ea[(int64_t)e * p.de + k] : 0.f;
-          if (!ok) continue;
-          float q[VEC];
-          if constexpr (VEC == 4) {
-            const float4 q4 = *(const float4*)(p.Q + (int64_t)s * p.ldq + ch);
-            q[0] = q4.x; q[1 % VEC] = q4.y; q[2 % VEC] = q4.z; q[3 % VEC] = q4.w;
-          } else {
-#pragma unroll
-            for (int v = 0; v < VEC; v++) q[v] = p.Q[(int64_t)s * p.ldq + ch + v];
-          }
-#pragma unroll
-          for (int v = 0; v < VEC; v++) {
-            float r = q[v];
-#pragma unroll
-            for (int k = 0; k < DEP; k++) r = __builtin_fmaf(we[v][k], a[k], r);
-            if (AGGR == RGNN_AGGR_MIN) {
-              s1[v] = fminf(s1[v], r);
-            } else {
-              if (e == beg) q0[v] = r;
-              const float dd = r - q0[v];
-              s1[v] += dd;
-              s2[v] = __builtin_fmaf(dd, dd, s2[v]);
-            }
-          }
-        }
-        if (!ok) continue;
-        const int cnt = end - beg;
-        float o[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; v++) {
-          if (AGGR == RGNN_AGGR_MIN) {
-            float x = 0.f;                             // empty segment -> exactly 0 (torch-scatter), not +inf
-            if (cnt > 0) {
-              float pn = p.p_bias ? p.p_bias[ch + v] : 0.f;
-              if (p.P) pn += p.P[node * p.ldp + ch + v];
-              x = pn + s1[v];
-            }
-            o[v] = x;
-          } else {
-            o[v] = mp_ext_finish<AGGR>(s1[v], s2[v], cnt);
-          }
-          amax = fmaxf(amax, fabsf(o[v]));
-        }
-        float* dst = p.out + node * p.ldo + ch;
-        if constexpr (VEC == 4) *(float4*)dst = make_float4(o[0], o[1 % VEC], o[2 % VEC], o[3 % VEC]);
-        else
-#pragma unroll
-          for (int v = 0; v < VEC; v++) dst[v] = o[v];
-      }
-    }
-  }
-  if (p.out_absmax) {                                  // one atomic per wave, spread over the slots of the bound (rgnn.h)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-    if (lane == 0) atomicMax((unsigned int*)p.out_absmax + (gw & (RGNN_BOUND_SLOTS - 1)), __float_as_uint(amax));
-  }
-}
-
-// The same three reductions on the schedule of k_mpnn_fast (d % 4 == 0, a chunk table, de <= 8): persistent waves on per-XCD
-// ticket queues of work-balanced chunks, a chunk's indices and attributes by coalesced loads and v_readlane, the row gathers two
-// edges ahead.  k_mpnn_ext above is a chain of dependent loads per edge and measures four times the time of `mean` on the C2
-// graph; this form moves the same bytes on the same schedule as `mean`.  Registers: 4 DEP (W_e) + 16 (rows in flight) + 4 (q)
-// + 12 (q_0 and the two sums; min: the minimum and the target term) per channel group -- far below what three waves per SIMD
-// leave, no scratch (MEASUREMENTS.md 4.2).
-template <int AGGR, int NCH, int DEP>
-__global__ __launch_bounds__(MP_THREADS) __attribute__((amdgpu_waves_per_eu(3))) void k_mpnn_fast_ext(
-    const float* __restrict__ P, int64_t ldp, const float* __restrict__ p_bias, const float* __restrict__ Q, int64_t ldq,
-    const float* __restrict__ We, int64_t ldwe, const float* __restrict__ ea, int de, const int32_t* __restrict__ rowptr,
-    const int32_t* __restrict__ src, const int32_t* __restrict__ order, const int32_t* __restrict__ chunk_start, int n_chunks,
-    int32_t* __restrict__ queue, int64_t n, int d, float* __restrict__ out, int64_t ldo, float* __restrict__ out_absmax) {
-  constexpr int EPL = 64 / DEP;  // edges whose attributes fit one 64-lane load
-  const int lane = threadIdx.x & 63;
-  const int xcd = blockIdx.x & 7;
-  const int c_lo = (int)((int64_t)n_chunks * xcd / 8), c_hi = (int)((int64_t)n_chunks * (xcd + 1) / 8);
-  int32_t* ticket = queue + (blockIdx.y * 8 + xcd) * 16;  // one counter per (channel block, XCD), 64 B apart
-
-  int ch[NCH];
-  bool ok[NCH];
-  float4 we[NCH][DEP];
-#pragma unroll
-  for (int t = 0; t < NCH; t++) {
-    const int c = (blockIdx.y * NCH + t) * 256 + lane * 4;
-    ok[t] = c < d;
-    ch[t] = ok[t] ? c : 0;
-#pragma unroll
-    for (int k = 0; k < DEP; k++) {
-      const bool kk = ok[t] && k < de;
-      we[t][k].x = kk ? We[(int64_t)(ch[t] + 0) * ldwe + k] : 0.f;
-      we[t][k].y = kk ? We[(int64_t)(ch[t] + 1) * ldwe + k] : 0.f;
-      we[t][k].z = kk ? We[(int64_t)(ch[t] + 2) * ldwe + k] : 0.f;
-      we[t][k].w = kk ? We[(int64_t)(ch[t] + 3) * ldwe + k] : 0.f;
-    }
-  }
-  const int ea_edge = lane / DEP, ea_k = lane % DEP;  // which attribute this lane fetches in an attribute block
-  float amax = 0.f;
-
-  for (;;) {
-    int cidx = 0;
-    if (lane == 0) cidx = c_lo + atomicAdd(ticket, 1);
-    cidx = __builtin_amdgcn_readfirstlane(cidx);
-    if (cidx >= c_hi) {
-      if (lane == 0) {                                   // the last wave of a queue to run dry puts both counters back to zero
-        const int waves = (int)(gridDim.x >> 3) * MP_WAVES;
-        if (atomicAdd(ticket + 1, 1) == waves - 1) { ticket[0] = 0; ticket[1] = 0; }
-      }
-      break;
-    }
-    const int pos_beg = __builtin_amdgcn_readfirstlane(chunk_start[cidx]);
-    const int cn = __builtin_amdgcn_readfirstlane(chunk_start[cidx + 1]) - pos_beg;  // targets of this chunk (<= 63)
-    if (cn <= 0) continue;
-    const int my_rp = rowptr[pos_beg + min(lane, cn)];
-    const int my_node = order ? order[pos_beg + min(lane, cn - 1)] : (pos_beg + min(lane, cn - 1));
-    const int e_lo = __builtin_amdgcn_readlane(my_rp, 0);
-    const int e_hi = __builtin_amdgcn_readlane(my_rp, cn);
-
-    int ni = 0, node = 0, node_end = 0, cnt = 0;       // target cursor (all wave-uniform)
-    bool first = true;                                 // the next edge opens its segment (var / std: it becomes q_0)
-    float4 s1[NCH], s2[NCH], q0[NCH];                  // min: s1 = running minimum, q0 = target term; var / std: sum d, sum d^2, q_0
-    auto open_node = [&](int i) {
-      node = __builtin_amdgcn_readlane(my_node, i);
-      node_end = __builtin_amdgcn_readlane(my_rp, i + 1);
-      cnt = node_end - __builtin_amdgcn_readlane(my_rp, i);
-      first = true;
-      const float init = (AGGR == RGNN_AGGR_MIN) ? INFINITY : 0.f;
-#pragma unroll
-      for (int t = 0; t < NCH; t++) {
-        s1[t] = make_float4(init, init, init, init);
-        s2[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-        q0[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (AGGR == RGNN_AGGR_MIN && cnt > 0) {
-          if (p_bias) q0[t] = *(const float4*)(p_bias + ch[t]);
-          if (P) {
-            const float4 x = *(const float4*)(P + (int64_t)node * ldp + ch[t]);
-            q0[t].x += x.x; q0[t].y += x.y; q0[t].z += x.z; q0[t].w += x.w;
-          }
-        }
-      }
-    };
-    auto close_node = [&]() {
-#pragma unroll
-      for (int t = 0; t < NCH; t++) {
-        if (!ok[t]) continue;
-        float4 o;
-        if (AGGR == RGNN_AGGR_MIN) {
-          o = make_float4(0.f, 0.f, 0.f, 0.f);           // empty segment -> exactly 0 (torch-scatter), not +inf
-          if (cnt > 0) o = make_float4(q0[t].x + s1[t].x, q0[t].y + s1[t].y, q0[t].z + s1[t].z, q0[t].w + s1[t].w);
-        } else {
-          o = make_float4(mp_ext_finish<AGGR>(s1[t].x, s2[t].x, cnt), mp_ext_finish<AGGR>(s1[t].y, s2[t].y, cnt),
-                          mp_ext_finish<AGGR>(s1[t].z, s2[t].z, cnt), mp_ext_finish<AGGR>(s1[t].w, s2[t].w, cnt));
-        }
-        amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
-        *(float4*)(out + (int64_t)node * ldo + ch[t]) = o;
-      }
-    };
-    open_node(0);
-
-    // flat edge stream [e_lo, e_hi): 64 indices per coalesced load, row gathers two edges ahead, across node borders
-    int src_cur = (e_lo + lane < e_hi) ? src[e_lo + lane] : 0;
-    float4 qa[NCH], qb[NCH];
-    float my_ea = 0.f;
-    for (int eb = e_lo; eb < e_hi; eb += 64) {
-      const int src_nxt = (eb + 64 + lane < e_hi) ? src[eb + 64 + lane] : 0;
-      auto row_of = [&](int j, float4* q) {  // Q row of edge eb + j (clamped to the stream; surplus gathers are discarded)
-        const int jj = min(j, e_hi - 1 - eb);
-        const int s = (jj < 64) ? __builtin_amdgcn_readlane(src_cur, jj) : __builtin_amdgcn_readlane(src_nxt, jj - 64);
-#pragma unroll
-        for (int t = 0; t < NCH; t++) q[t] = *(const float4*)(Q + (int64_t)s * ldq + ch[t]);
-      };
-      auto attr_block = [&](int blk) {  // attributes of edges eb + [blk*EPL, blk*EPL+EPL), one value per lane
-        const int e = eb + blk * EPL + ea_edge;
-        return (e < e_hi && ea_k < de) ? ea[(int64_t)e * de + ea_k] : 0.f;
-      };
-      if (eb == e_lo) {
-        row_of(0, qa); row_of(1, qb);
-        my_ea = attr_block(0);
-      }
-      const int nbk = min(64, e_hi - eb);
-      for (int j = 0; j < nbk; j += 2) {
-        float4 qc[NCH], qd[NCH];
-        row_of(j + 2, qc); row_of(j + 3, qd);
-        float ea_next = my_ea;
-        if (((j + 2) % EPL) == 0) ea_next = attr_block((j + 2) / EPL);
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-          const int e = eb + j + u;
-          if (e >= e_hi) break;
-          while (e >= node_end) {  // crossed into the next target (possibly over empty ones)
-            close_node();
-            ni++;
-            open_node(ni);
-          }
-          float4 q[NCH];
-#pragma unroll
-          for (int t = 0; t < NCH; t++) q[t] = (u == 0) ? qa[t] : qb[t];
-          const int lane0 = ((j + u) % EPL) * DEP;
-#pragma unroll
-          for (int k = 0; k < DEP; k++) {
-            const float ak = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_ea), lane0 + k));
-#pragma unroll
-            for (int t = 0; t < NCH; t++) {
-              q[t].x = __builtin_fmaf(we[t][k].x, ak, q[t].x); q[t].y = __builtin_fmaf(we[t][k].y, ak, q[t].y);
-              q[t].z = __builtin_fmaf(we[t][k].z, ak, q[t].z); q[t].w = __builtin_fmaf(we[t][k].w, ak, q[t].w);
-            }
-          }
-#pragma unroll
-          for (int t = 0; t < NCH; t++) {
-            if (AGGR == RGNN_AGGR_MIN) {
-              s1[t].x = fminf(s1[t].x, q[t].x); s1[t].y = fminf(s1[t].y, q[t].y);
-              s1[t].z = fminf(s1[t].z, q[t].z); s1[t].w = fminf(s1[t].w, q[t].w);
-            } else {
-              if (first) q0[t] = q[t];
-              const float4 dd = make_float4(q[t].x - q0[t].x, q[t].y - q0[t].y, q[t].z - q0[t].z, q[t].w - q0[t].w);
-              s1[t].x += dd.x; s1[t].y += dd.y; s1[t].z += dd.z; s1[t].w += dd.w;
-              s2[t].x = __builtin_fmaf(dd.x, dd.x, s2[t].x); s2[t].y = __builtin_fmaf(dd.y, dd.y, s2[t].y);
-              s2[t].z = __builtin_fmaf(dd.z, dd.z, s2[t].z); s2[t].w = __builtin_fmaf(dd.w, dd.w, s2[t].w);
-            }
-          }
-          first = false;
-        }
-#pragma unroll
-        for (int t = 0; t < NCH; t++) { qa[t] = qc[t]; qb[t] = qd[t]; }
-        my_ea = ea_next;
-      }
-      src_cur = src_nxt;
-    }
-    // the target that was open when the stream ended, then any trailing targets without edges
-    for (;;) {
-      close_node();
-      if (++ni >= cn) break;
-      open_node(ni);
-    }
-  }
-  if (out_absmax) {                                    // one atomic per wave, spread over the slots of the bound (rgnn.h)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-    if (lane == 0)
-      atomicMax((unsigned int*)out_absmax + (((blockIdx.y * gridDim.x + blockIdx.x) * MP_WAVES + (threadIdx.x >> 6)) & (RGNN_BOUND_SLOTS - 1)),
-                __float_as_uint(amax));
-  }
-}
-
-template <int AGGR>
-void dispatch_ext(MpParams& p, hipStream_t s) {
-  const bool rows16 = (p.d % 4 == 0) && (p.ldq % 4 == 0) && (p.ldo % 4 == 0) && (((uintptr_t)p.Q & 15) == 0) &&
-                      (((uintptr_t)p.out & 15) == 0);
-  const bool term16 = AGGR != RGNN_AGGR_MIN || ((p.P == nullptr || ((p.ldp % 4 == 0) && (((uintptr_t)p.P & 15) == 0))) &&
-                                                (p.p_bias == nullptr || (((uintptr_t)p.p_bias & 15) == 0)));
-  // (RGNN_MPNN_QUEUE_INTS holds the ticket counters of 8 channel blocks: wider messages stay on k_mpnn_ext)
-  const bool queues_fit = p.d <= 8 * 256 * ((AGGR == RGNN_AGGR_MIN || p.de <= 4) ? 2 : 1);
-  if (rows16 && term16 && queues_fit && p.chunk_start != nullptr && p.de <= 8) {          // the schedule of k_mpnn_fast (see dispatch<MODE>)
-    // two channel groups per lane past 256 channels, as k_mpnn_fast -- except var / std with 5 .. 8 attributes: q_0 and two sums per
-    // group next to 64 weight registers spill under three waves per SIMD (56 / 64 bytes of scratch): one group, twice the blocks in y
-    const int nch = (p.d > 256 && (AGGR == RGNN_AGGR_MIN || p.de <= 4)) ? 2 : 1;
-    const unsigned ny = (unsigned)((p.d + 256 * nch - 1) / (256 * nch));
-    int64_t blocks = (p.n_chunks + MP_WAVES - 1) / MP_WAVES;
-    if (blocks > 256 * 3) blocks = 256 * 3;                                 // persistent: 3 workgroups of 4 waves per CU
-    blocks = (blocks + 7) / 8 * 8;
-    const dim3 grid((unsigned)blocks, ny), block(MP_THREADS);
-    int32_t* queue = const_cast<int32_t*>(p.chunk_start) + p.n_chunks + 1;  // ticket counters behind the chunk table, left at zero
-#define RGNN_MPFE(NCH, DEP)                                                                                               \
-  hipLaunchKernelGGL((k_mpnn_fast_ext<AGGR, NCH, DEP>), grid, block, 0, s, p.P, p.ldp, p.p_bias, p.Q, p.ldq, p.We, p.ldwe, p.ea, \
-                     p.de, p.rowptr, p.src, p.order, p.chunk_start, p.n_chunks, queue, p.n, p.d, p.out, p.ldo, p.out_absmax)
-    if (nch == 2) {
-      if (p.de <= 4) RGNN_MPFE(2, 4);
-      else if constexpr (AGGR == RGNN_AGGR_MIN) RGNN_MPFE(2, 8);
-    } else if (p.de <= 4) RGNN_MPFE(1, 4);
-    else RGNN_MPFE(1, 8);
-#undef RGNN_MPFE
-    return;
-  }
-  const bool vec4 = (p.d % 4 == 0) && (p.ldq % 4 == 0) && (p.ldo % 4 == 0) && (((uintptr_t)p.Q & 15) == 0) &&
-                    (((uintptr_t)p.out & 15) == 0) && p.de <= 8;
-  const int64_t target_waves = 256 * 16;
-  int64_t chunk = (p.n + target_waves - 1) / target_waves;
-  if (chunk < 8) chunk = 8;
-  p.chunk = chunk;
-  const int64_t waves = (p.n + chunk - 1) / chunk;
-  const dim3 grid((unsigned)((waves + MP_WAVES - 1) / MP_WAVES)), block(MP_THREADS);
-#define RGNN_MPE(VEC, DEP) hipLaunchKernelGGL((k_mpnn_ext<AGGR, VEC, DEP>), grid, block, 0, s, p)
-  if (vec4) { if (p.de <= 4) RGNN_MPE(4, 4); else RGNN_MPE(4, 8); }
-  else if (p.de <= 4) RGNN_MPE(1, 4);
-  else if (p.de <= 16) RGNN_MPE(1, 16);
-  else RGNN_MPE(1, 32);
-#undef RGNN_MPE
-}
-
-// rows [E, d] in CSR order -> out [n, d], codes 3 - 5: the reductions literally over the rows (no target term here)
-template <int AGGR>
-__global__ __launch_bounds__(256) void k_segment_reduce_ext(const float* __restrict__ rows, int64_t ldr,
-                                                           const int32_t* __restrict__ rowptr,
-                                                           const int32_t* __restrict__ order, int64_t n, int d,
-                                                           float* __restrict__ out, int64_t ldo) {
-  const int lane = threadIdx.x & 63;
-  const int64_t pos = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (pos >= n) return;
-  const int64_t node = order ? (int64_t)order[pos] : pos;
-  const int beg = rowptr[pos], end = rowptr[pos + 1];
-  for (int c = lane; c < d; c += 64) {
-    float s1 = (AGGR == RGNN_AGGR_MIN) ? INFINITY : 0.f, s2 = 0.f;
-    const float r0 = (end > beg) ? rows[(int64_t)beg * ldr + c] : 0.f;
-    for (int e = beg; e < end; e++) {
-      const float v = rows[(int64_t)e * ldr + c];
-      if (AGGR == RGNN_AGGR_MIN) s1 = fminf(s1, v);
-      else {
-        const float dd = v - r0;
-        s1 += dd;
-        s2 = __builtin_fmaf(dd, dd, s2);
-      }
-    }
-    float x;
-    if (AGGR == RGNN_AGGR_MIN) x = (end > beg) ? s1 : 0.f;
-    else x = mp_ext_finish<AGGR>(s1, s2, end - beg);
-    out[node * ldo + c] = x;
+    typename R::State st = R::init();
+    for (int e = beg; e < end; e++) R::step(st, rows[(int64_t)e * ldr + c], e == beg);
+    out[node * ldo + c] = R::reduced(st, end - beg);
   }
 }
 
@@ -1128,7 +1032,7 @@ extern "C" int rgnn_mpnn_aggregate(const float* P, int64_t ldp, const float* p_b
   RGNN_CHECK_ARG((flags & ~RGNN_MPNN_SKIP_EMPTY_ROWS) == 0, "unknown flags");
   MpParams p;
   p.P = P; p.ldp = ldp; p.p_bias = p_bias; p.Q = Q; p.ldq = ldq; p.We = We; p.ldwe = ldwe; p.ea = edge_attr_sorted;
-  p.de = de; p.rowptr = rowptr_t; p.src = src_sorted; p.order = node_order; p.n = n; p.d = d; p.aggr = aggr; p.relu = 0;
+  p.de = de; p.rowptr = rowptr_t; p.src = src_sorted; p.order = node_order; p.n = n; p.d = d; p.relu = 0;
   p.chunk_start = chunk_start; p.n_chunks = n_chunks;
   p.skip_empty = (flags & RGNN_MPNN_SKIP_EMPTY_ROWS) ? 1 : 0;   // (honoured by the max kernel; the others write the zeros)
   p.out = out;
@@ -1136,12 +1040,9 @@ extern "C" int rgnn_mpnn_aggregate(const float* P, int64_t ldp, const float* p_b
   p.arg_out = nullptr;
   p.out_absmax = out_absmax;
   rgnn_prof_begin((hipStream_t)stream);
-  int which = 2;                                                // (codes 3 - 5: k_mpnn_ext writes every row and tracks |out| itself)
-  if (aggr == RGNN_AGGR_MIN) dispatch_ext<RGNN_AGGR_MIN>(p, (hipStream_t)stream);
-  else if (aggr == RGNN_AGGR_VAR) dispatch_ext<RGNN_AGGR_VAR>(p, (hipStream_t)stream);
-  else if (aggr == RGNN_AGGR_STD) dispatch_ext<RGNN_AGGR_STD>(p, (hipStream_t)stream);
-  else which = dispatch<0>(p, (hipStream_t)stream);
+  const int which = dispatch_aggr(aggr, p, (hipStream_t)stream);
   rgnn_prof_end((hipStream_t)stream);
+  RGNN_CHECK_ARG(which >= 0, "unknown aggregation");
   if (out_absmax != nullptr && which != 2) {
     // another kernel took the launch (mean / add, per-target rows, wide edge attributes): one pass over the rows it wrote --
     // those kernels write every row, the zeros of empty targets included
@@ -1165,14 +1066,14 @@ extern "C" int rgnn_mpnn_aggregate_max_arg(const float* p_bias, const float* Q, 
   RGNN_CHECK_ARG((flags & ~RGNN_MPNN_SKIP_EMPTY_ROWS) == 0, "unknown flags");
   MpParams p;
   p.P = nullptr; p.ldp = 0; p.p_bias = p_bias; p.Q = Q; p.ldq = ldq; p.We = We; p.ldwe = ldwe; p.ea = edge_attr_sorted;
-  p.de = de; p.rowptr = rowptr_t; p.src = src_sorted; p.order = node_order; p.n = n; p.d = d; p.aggr = RGNN_AGGR_MAX; p.relu = 0;
+  p.de = de; p.rowptr = rowptr_t; p.src = src_sorted; p.order = node_order; p.n = n; p.d = d; p.relu = 0;
   p.chunk_start = chunk_start; p.n_chunks = n_chunks;
   p.skip_empty = (flags & RGNN_MPNN_SKIP_EMPTY_ROWS) ? 1 : 0;
   p.out = out; p.ldo = ldo;
   p.arg_out = (d % 8 == 0 && ((uintptr_t)arg_out & 15) == 0) ? arg_out : nullptr;
   p.out_absmax = out_absmax;
   rgnn_prof_begin((hipStream_t)stream);
-  const int which = dispatch<0>(p, (hipStream_t)stream);
+  const int which = dispatch<RGNN_AGGR_MAX>(p, (hipStream_t)stream);
   rgnn_prof_end((hipStream_t)stream);
   *arg_written = ((which >= 1 && p.arg_out != nullptr) ? 1 : 0) | ((which == 2) ? 2 : 0);
   if (out_absmax != nullptr && which != 2) {                    // (another kernel took the launch: it wrote every row -- one pass over them)
@@ -1194,11 +1095,11 @@ extern "C" int rgnn_mpnn_edge_hidden(const float* P, int64_t ldp, const float* p
   RGNN_CHECK_ARG(hidden, "null hidden");
   MpParams p;
   p.P = P; p.ldp = ldp; p.p_bias = p_bias; p.Q = Q; p.ldq = ldq; p.We = We; p.ldwe = ldwe; p.ea = edge_attr_sorted;
-  p.de = de; p.rowptr = rowptr_t; p.src = src_sorted; p.order = node_order; p.n = n; p.d = d; p.aggr = 0; p.relu = relu;
+  p.de = de; p.rowptr = rowptr_t; p.src = src_sorted; p.order = node_order; p.n = n; p.d = d; p.relu = relu;
   p.chunk_start = chunk_start; p.n_chunks = n_chunks; p.skip_empty = 0; p.arg_out = nullptr; p.out_absmax = nullptr;
   p.out = hidden;
   p.ldo = ldh;
-  dispatch<1>(p, (hipStream_t)stream);
+  dispatch<MP_EMIT>(p, (hipStream_t)stream);
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
 }
@@ -1207,15 +1108,17 @@ extern "C" int rgnn_segment_reduce(const float* rows, int64_t ldr, const int32_t
                                    int64_t n, int32_t d, int32_t aggr, float* out, int64_t ldo, rgnn_stream_t stream) {
   if (n == 0) return RGNN_OK;
   RGNN_CHECK_ARG(rowptr_t && out && d >= 1 && aggr >= 0 && aggr <= RGNN_AGGR_STD, "bad arguments");
-#define RGNN_SRX(A) hipLaunchKernelGGL((k_segment_reduce_ext<A>), dim3(rgnn_blocks(n, 4)), dim3(256), 0, (hipStream_t)stream, rows, ldr, \
-                                       rowptr_t, node_order, n, d, out, ldo)
-  if (aggr == RGNN_AGGR_MIN) RGNN_SRX(RGNN_AGGR_MIN);
-  else if (aggr == RGNN_AGGR_VAR) RGNN_SRX(RGNN_AGGR_VAR);
-  else if (aggr == RGNN_AGGR_STD) RGNN_SRX(RGNN_AGGR_STD);
-  else
-    hipLaunchKernelGGL(k_segment_reduce, dim3(rgnn_blocks(n, 4)), dim3(256), 0, (hipStream_t)stream, rows, ldr, rowptr_t,
-                       node_order, n, d, aggr, out, ldo);
-#undef RGNN_SRX
+  switch (aggr) {
+#define RGNN_SR(A)                                                                                                             \
+  case A:                                                                                                                      \
+    hipLaunchKernelGGL((k_segment_reduce<A>), dim3(rgnn_blocks(n, 4)), dim3(256), 0, (hipStream_t)stream, rows, ldr, rowptr_t, \
+                       node_order, n, d, out, ldo);                                                                            \
+    break
+    RGNN_SR(RGNN_AGGR_MAX); RGNN_SR(RGNN_AGGR_MEAN); RGNN_SR(RGNN_AGGR_ADD);
+    RGNN_SR(RGNN_AGGR_MIN); RGNN_SR(RGNN_AGGR_VAR); RGNN_SR(RGNN_AGGR_STD);
+#undef RGNN_SR
+    default: RGNN_CHECK_ARG(false, "unknown aggregation");
+  }
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
 }

@@ -1,6 +1,6 @@
-"""Aggregations min | var | std (RGNN_AGGR_MIN / _VAR / _STD) on the device: the per-edge kernels k_mpnn_ext and k_mpnn_fast_ext (the
-one a launch with a chunk table takes where d % 4 == 0 and de <= 8: every forward case runs with and without the table), the row kernels
-k_segment_reduce_ext / k_segment_reduce_bwd_ext, the backward kernels (k_mpnn_bwd_arg with the comparison turned round,
+"""Aggregations min | var | std (RGNN_AGGR_MIN / _VAR / _STD) on the device: the per-edge kernels k_mpnn and k_mpnn_fast at AGGR 3 - 5 (the
+latter is the one a launch with a chunk table takes where d % 4 == 0 and de <= 8: every forward case runs with and without the table), the
+row kernels k_segment_reduce / k_segment_reduce_bwd at AGGR 3 - 5, the backward kernels (k_mpnn_bwd_arg with the comparison turned round,
 k_mpnn_bwd_coef / _edge_var / _src_var) on the hand-built CSRs of tests/mpnn_csr_cases.py and tests/mpnn_bwd_cases.py, and the conv
 layers, the model, HotPath and per-frame BatchNorm with the three names.  Reference: tests/aggr_ext_oracle.py (the literal formulas
 of torch_geometric 2.1.0 / torch-scatter in torch index ops, float64; the float32 evaluation of the same, target term inside the
@@ -126,7 +126,7 @@ def test_min_is_bit_equal_on_integers(ops, name):
             exp = reference(c, Q, We, ea, P, b, order, "min", torch.float64)
             has = torch.zeros(c.n, dtype=torch.bool)
             has[target_nodes(c, order)] = True
-            for chunks in (False, True):                                     # k_mpnn_ext / (d % 4 == 0) k_mpnn_fast_ext
+            for chunks in (False, True):                                     # k_mpnn / (d % 4 == 0) k_mpnn_fast
                 out = launch(ops, c, order, Q, We, ea, P, b, "min", chunks=chunks).cpu()
                 what = f"{name} d={d} de={de} order={order is not None} P={with_p} negative={negative} chunks={chunks}"
                 assert torch.equal(out, exp.to(torch.float32)), f"{what}: {int((out != exp.to(torch.float32)).sum())} elements differ"
@@ -173,7 +173,7 @@ def test_var_std_with_exact_sums(ops, name, aggr):
         deg_node[torch.from_numpy(np.arange(c.n) if order is None else order.numpy().astype(np.int64))] = torch.from_numpy(c.deg)
         flat = (deg_node <= 1) | equal_seg                                  # no edge, one edge, or equal messages
         fill = S0_F32 if aggr == "std" else torch.tensor(0.0)
-        for chunks in (False, True):                                         # k_mpnn_ext / (d % 4 == 0, de <= 8) k_mpnn_fast_ext
+        for chunks in (False, True):                                         # k_mpnn / (d % 4 == 0, de <= 8) k_mpnn_fast
             out = launch(ops, c, order, Q, We, ea, P, b, aggr, chunks=chunks).cpu()
             err = (out.double() - exp).abs()
             what = f"{name} {aggr} d={d} de={de} order={order is not None} P={with_p} chunks={chunks}"
@@ -245,8 +245,8 @@ def test_a_common_offset_of_1e3_costs_no_digits(ops, aggr, de):
 
 @pytest.mark.parametrize("aggr", ax.AGGRS)
 def test_both_per_edge_kernels_give_the_same_bits_past_256_channels(ops, aggr):
-    """More than 256 channels: k_mpnn_fast_ext takes two channel groups per lane (min; var / std with at most 4 attributes) or several
-    blocks in y (var / std with 5 .. 8 attributes), k_mpnn_ext several passes.  Both do the same operations on a channel in the same
+    """More than 256 channels: k_mpnn_fast takes two channel groups per lane (min; var / std with at most 4 attributes) or several
+    blocks in y (var / std with 5 .. 8 attributes), k_mpnn several passes.  Both do the same operations on a channel in the same
     order: the same bits.  Against float64 at the yardsticks of the float test (min: 1e-5 of the largest result)."""
     for name in ("degrees_1_to_8/empty_ends", "leftover_blocks"):
         c = mc.case(name)
