@@ -474,8 +474,9 @@ int rgnn_batchnorm_finalize(const float* stats_a, int64_t panels_a, const int64_
  * postprocessor/inference.py:57-62, gnn/gnn_models.py:124-128): every frame is normalised with its own batch statistics; this
  * reproduces that in a batched launch.  table [dev] float [n_seg, RGNN_AFFINE_ROWS, n] receives the apply table of every segment; the running
  * statistics are walked through the segments in order (what a loop of single-frame forwards does), num_batches_tracked grows
- * by the number of non-empty segments.  seg_sums: [dev] scratch, double [n_seg, 2, n].  in_bound / out_bound: as in
- * rgnn_batchnorm_finalize (optional). */
+ * by the number of non-empty segments.  seg_sums: [dev] scratch, double [n_seg, 2, n]; on return it holds {mean, unbiased
+ * variance} per (segment, column) (zeros for an empty segment) -- the exact statistics rgnn_bn_segments_bwd reads.  in_bound /
+ * out_bound: as in rgnn_batchnorm_finalize (optional). */
 int rgnn_batchnorm_segments(const float* x, int64_t ldx, const int64_t* seg_ptr /*[dev] n_seg + 1*/, int64_t n_seg, int32_t n,
                             const float* gamma, const float* beta, float* running_mean, float* running_var,
                             int64_t* num_batches_tracked, float momentum, float eps, double* seg_sums, float* table,
@@ -843,6 +844,24 @@ int rgnn_bn_bwd_apply(const float* dy, int64_t lddy, const float* y /*or NULL*/,
 int rgnn_bn_bwd_coef(const float* fwd_stats, int64_t panels_f, const float* running_mean, const float* running_var,
                      const float* bwd_part, int64_t panels_b, int64_t m, int32_t n, const float* gamma, float eps,
                      int32_t use_batch, float* coef, float* dgamma, float* dbeta, rgnn_stream_t stream);
+/* Backward of the segment-scoped BatchNorm (rgnn_batchnorm_segments / rgnn_batchnorm_act_segments): segment s = rows
+ * [seg_ptr[s], seg_ptr[s + 1]) of m_s rows has its own statistics, so with g = dy (y == NULL) or dy masked by y > 0 (y = the saved
+ * output behind the fused ReLU) and xhat = (h - mu_s) r_s:
+ *     dx = gamma r_s (g - S1 / m_s - xhat S2 / m_s),  S1 = sum_rows g,  S2 = sum_rows g xhat,  dgamma = sum_s S2,  dbeta = sum_s S1.
+ * seg_stats: the forward's seg_sums as those entry points LEAVE it, double [n_seg, 2, n] = {mean, unbiased variance} per
+ * (segment, column) -- exact statistics, never the fp32 apply table divided by gamma.  A segment without rows contributes
+ * nothing; a segment of one row gets dx = 0 exactly, adds its g to dbeta and nothing to dgamma.  Rows outside every segment are
+ * not written.  seg_ptr is read on the device and every row range is clamped to [0, m].
+ * Workspace: seg_bsums, double [n_seg, 2, n] (S1, S2 per segment and column; written, then summed in segment order).
+ * Two launches: one block per (segment, 64-column slab) sums the slab, finishes its coefficients in float64 and writes dx (16-byte
+ * accesses when n and every row stride are multiples of 4 floats and the pointers 16-byte aligned; any width, stride and alignment
+ * otherwise); a thread per column adds dgamma / dbeta over the segments (skipped when both are NULL).  Deterministic: fixed
+ * summation order, no floating-point atomics.  dx_absmax: as in rgnn_bn_bwd_apply. */
+int rgnn_bn_segments_bwd(const float* dy, int64_t lddy, const float* y /*or NULL*/, int64_t ldy, const float* h, int64_t ldh,
+                         const int64_t* seg_ptr /*[dev] n_seg + 1*/, int64_t n_seg, int64_t m, int32_t n,
+                         const double* seg_stats, const float* gamma /*or NULL*/, float eps, double* seg_bsums, float* dx,
+                         int64_t lddx, float* dgamma /*or NULL*/, float* dbeta /*or NULL*/, float* dx_absmax /*or NULL*/,
+                         rgnn_stream_t stream);
 
 /* Backward of rgnn_segment_reduce: d_rows [E, d] (every row is written; rows of the forward input are needed for the
  * arg-max: the first row of a segment attaining the maximum receives dM[t, c]; mean / add: every row, / deg; min: the first row
@@ -936,6 +955,22 @@ int rgnn_detection_loss_bwd(const float* cls, int64_t ldc, int32_t n_classes, co
                             int32_t bg_index, float delta, float cls_loss_weight, float bb_loss_weight, const double* sums,
                             const float* grad_loss, float* d_cls, int64_t lddc, float* d_boxes, int64_t lddb,
                             rgnn_stream_t stream);
+/* The same loss with one result per group of rows -- group g = rows [group_ptr[g], group_ptr[g + 1]), group_ptr int64
+ * [n_groups + 1] on the device, every range clamped to [0, n] -- for steps that run several loader batches through one forward:
+ * the reference's loss is a per-loader-batch quantity.  sums: double [n_groups, 4], loss_out: float [n_groups, 3], per group as
+ * above (the weighted mean over the group's nodes; loss_bb = 0 for a group without object nodes or with a NaN Huber sum; an
+ * empty group has loss_cls = NaN like an empty batch).  One launch, no workspace.
+ * _bwd: d (sum_g coef[g] loss_g) / d cls and / d boxes, coef float [n_groups] on the device (NULL: all ones); rows outside every
+ * group get zeros.  Deterministic, no atomics. */
+int rgnn_detection_loss_segments(const float* cls, int64_t ldc, int32_t n_classes, const float* boxes, int64_t ldb,
+                                 int32_t box_width, const float* y, int64_t ldy, const float* class_weight, int64_t n,
+                                 const int64_t* group_ptr, int64_t n_groups, int32_t bg_index, float delta, float cls_loss_weight,
+                                 float bb_loss_weight, double* sums, float* loss_out, rgnn_stream_t stream);
+int rgnn_detection_loss_segments_bwd(const float* cls, int64_t ldc, int32_t n_classes, const float* boxes, int64_t ldb,
+                                     int32_t box_width, const float* y, int64_t ldy, const float* class_weight, int64_t n,
+                                     const int64_t* group_ptr, int64_t n_groups, int32_t bg_index, float delta,
+                                     float cls_loss_weight, float bb_loss_weight, const double* sums, const float* coef,
+                                     float* d_cls, int64_t lddc, float* d_boxes, int64_t lddb, rgnn_stream_t stream);
 
 /* ================================================================ ground-truth box targets (csrc/groundtruth.hip)
  * GroundTruthCreator.create_2D_bounding_boxes (preprocessor/radarscenes/dataset_creation.py:232-521): the box columns of `y`, the

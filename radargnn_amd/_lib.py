@@ -138,6 +138,8 @@ SIGNATURES = {
     "rgnn_bn_bwd_stats": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
     "rgnn_bn_bwd_apply": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp]),
     "rgnn_bn_bwd_coef": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_f32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_bn_segments_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp,
+                                     c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rgnn_mpnn_aggregate_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32,
                                         c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "rgnn_mpnn_max_bwd_supported": (c_i32, [c_i32, c_i32]),
@@ -177,6 +179,10 @@ SIGNATURES = {
                                     c_vp, c_vp, c_vp, c_vp]),
     "rgnn_detection_loss_bwd": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_i32, c_f32, c_f32,
                                         c_f32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "rgnn_detection_loss_segments": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32,
+                                             c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),
+    "rgnn_detection_loss_segments_bwd": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                                 c_i32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "rgnn_collate_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "rgnn_collate_edges": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_i64, c_vp]),
     "rgnn_stage_frames": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_i64]),

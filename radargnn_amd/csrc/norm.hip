@@ -938,3 +938,168 @@ extern "C" int rgnn_column_stats(const float* x, int64_t ldx, int64_t m, int32_t
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
 }
+
+namespace {
+// ---- Backward of the segment-scoped BatchNorm (rgnn_batchnorm_segments / rgnn_batchnorm_act_segments): grouped training steps, where
+// every loader batch of a step is normalised with its own statistics (gnn/trainer.py, gnn/autograd.py BatchNormSegmentsFn).
+// Per segment s of m_s rows and column c, with g = dy (masked by y > 0 behind the fused ReLU) and xhat = (h - mu) r:
+//     dh = gamma r (g - S1 / m_s - xhat S2 / m_s),   S1 = sum g,   S2 = sum g xhat,   d gamma = sum_s S2,   d beta = sum_s S1.
+// The forward's decomposition (k_bn_seg_fused): one block = one (segment, 64-channel slab), 16 waves; pass 1 sums the slab in
+// float64 about the segment's exact mean (read from the statistics the forward left), the 64 first threads finish the
+// coefficients in float64, pass 2 reads the slab again (L2) and writes
+//     dh = A g + B (h - mu) + C,   A = gamma r,   B = -A r^2 S2h / m_s,   C = -A S1 / m_s,   S2h = sum g (h - mu)   (S2 = r S2h)
+// in float64 as well, rounded once: in a short segment the three terms cancel (two rows: dh = O(eps / var) of each term), and
+// float32 coefficients would leave their rounding in what remains.  CPL = 4: a lane owns four channels and
+// a wave four rows (16-byte accesses); CPL = 1: a lane owns one channel (any width, stride and alignment).  Sums in a fixed
+// order, no atomics on floating-point values.  A segment of one row gets dh = 0 exactly (A = B = C = 0).
+template <int CPL>
+__global__ __launch_bounds__(1024) void k_bn_seg_bwd(const float* __restrict__ dy, int64_t lddy, const float* __restrict__ y, int64_t ldy,
+                                                    const float* __restrict__ h, int64_t ldh, const int64_t* __restrict__ seg_ptr,
+                                                    int64_t m, int n, const double* __restrict__ seg_stats /*[S][2][n]: mean, unbiased variance*/,
+                                                    const float* __restrict__ gamma, float eps, double* __restrict__ seg_bsums /*[S][2][n]: S1, S2*/,
+                                                    float* __restrict__ dx, int64_t lddx, float* __restrict__ dx_absmax) {
+  constexpr int LPR = 64 / CPL;                         // lanes across a row of the slab
+  constexpr int RG = 16 * (64 / LPR);                   // row groups of the block: 16 waves x rows per wave
+  __shared__ double red[2][16][64];
+  __shared__ double cf[3][64];                          // A, B, C of the slab's channels
+  const int f = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lc = (lane % LPR) * CPL;                    // the lane's first channel inside the slab
+  const int rg = wave * (64 / LPR) + lane / LPR;
+  const int c0 = blockIdx.y * 64 + lc;
+  int64_t r0 = seg_ptr[f], r1 = seg_ptr[f + 1];         // clamped to [0, m]: a malformed pointer gives wrong numbers, nothing else
+  r0 = r0 < 0 ? 0 : (r0 > m ? m : r0);
+  r1 = r1 < r0 ? r0 : (r1 > m ? m : r1);
+  const int64_t rows = r1 - r0;
+  const bool okc = c0 < n;                              // (CPL = 4 runs with n % 4 == 0: a lane's four channels stand or fall together)
+  double s1[CPL], s2[CPL], mu[CPL];
+#pragma unroll
+  for (int j = 0; j < CPL; j++) { s1[j] = 0.0; s2[j] = 0.0; mu[j] = (okc && rows > 0) ? seg_stats[((int64_t)f * 2 + 0) * n + c0 + j] : 0.0; }
+  if (okc) {
+    for (int64_t r = r0 + rg; r < r1; r += RG) {
+      if constexpr (CPL == 4) {
+        float4 g = *(const float4*)(dy + r * lddy + c0);
+        const float4 hh = *(const float4*)(h + r * ldh + c0);
+        if (y) {
+          const float4 yy = *(const float4*)(y + r * ldy + c0);
+          if (!(yy.x > 0.f)) g.x = 0.f;
+          if (!(yy.y > 0.f)) g.y = 0.f;
+          if (!(yy.z > 0.f)) g.z = 0.f;
+          if (!(yy.w > 0.f)) g.w = 0.f;
+        }
+        const float gv[4] = {g.x, g.y, g.z, g.w}, hv[4] = {hh.x, hh.y, hh.z, hh.w};
+#pragma unroll
+        for (int j = 0; j < CPL; j++) { s1[j] += (double)gv[j]; s2[j] += (double)gv[j] * ((double)hv[j] - mu[j]); }
+      } else {
+        float g = dy[r * lddy + c0];
+        if (y && !(y[r * ldy + c0] > 0.f)) g = 0.f;
+        s1[0] += (double)g; s2[0] += (double)g * ((double)h[r * ldh + c0] - mu[0]);
+      }
+    }
+  }
+  // the rows a wave covers at once (CPL = 4: lanes l, l ^ 16, l ^ 32, l ^ 48), then the 16 waves through LDS: a fixed order
+#pragma unroll
+  for (int j = 0; j < CPL; j++) {
+#pragma unroll
+    for (int o = LPR; o < 64; o <<= 1) { s1[j] += __shfl_xor(s1[j], o, 64); s2[j] += __shfl_xor(s2[j], o, 64); }
+    if (lane < LPR) { red[0][wave][lc + j] = s1[j]; red[1][wave][lc + j] = s2[j]; }
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const int c = blockIdx.y * 64 + threadIdx.x;
+    double A = 0.0, B = 0.0, C = 0.0;
+    if (c < n) {
+      double t1 = 0.0, t2 = 0.0;
+#pragma unroll
+      for (int i = 0; i < 16; i++) { t1 += red[0][i][threadIdx.x]; t2 += red[1][i][threadIdx.x]; }
+      double S2 = 0.0;
+      if (rows > 1) {
+        const double var = seg_stats[((int64_t)f * 2 + 1) * n + c] * (double)(rows - 1) / (double)rows;   // biased, from the unbiased one
+        const double rstd = 1.0 / sqrt((var > 0.0 ? var : 0.0) + (double)eps);
+        const double gm = gamma ? (double)gamma[c] : 1.0;
+        A = gm * rstd; B = -A * rstd * rstd * t2 / (double)rows; C = -A * t1 / (double)rows;
+        S2 = t2 * rstd;
+      }
+      seg_bsums[((int64_t)f * 2 + 0) * n + c] = rows > 0 ? t1 : 0.0;
+      seg_bsums[((int64_t)f * 2 + 1) * n + c] = S2;       // (one row: xhat = 0, nothing for d gamma)
+    }
+    cf[0][threadIdx.x] = A; cf[1][threadIdx.x] = B; cf[2][threadIdx.x] = C;
+  }
+  __syncthreads();
+  float amax = 0.f;
+  if (okc) {
+    double A[CPL], B[CPL], C[CPL];
+#pragma unroll
+    for (int j = 0; j < CPL; j++) { A[j] = cf[0][lc + j]; B[j] = cf[1][lc + j]; C[j] = cf[2][lc + j]; }
+    for (int64_t r = r0 + rg; r < r1; r += RG) {
+      if constexpr (CPL == 4) {
+        float4 g = *(const float4*)(dy + r * lddy + c0);
+        const float4 hh = *(const float4*)(h + r * ldh + c0);
+        if (y) {
+          const float4 yy = *(const float4*)(y + r * ldy + c0);
+          if (!(yy.x > 0.f)) g.x = 0.f;
+          if (!(yy.y > 0.f)) g.y = 0.f;
+          if (!(yy.z > 0.f)) g.z = 0.f;
+          if (!(yy.w > 0.f)) g.w = 0.f;
+        }
+        float4 v;
+        v.x = (float)(A[0] * (double)g.x + (B[0] * ((double)hh.x - mu[0]) + C[0])); v.y = (float)(A[1] * (double)g.y + (B[1] * ((double)hh.y - mu[1]) + C[1]));
+        v.z = (float)(A[2] * (double)g.z + (B[2] * ((double)hh.z - mu[2]) + C[2])); v.w = (float)(A[3] * (double)g.w + (B[3] * ((double)hh.w - mu[3]) + C[3]));
+        *(float4*)(dx + r * lddx + c0) = v;
+        amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+      } else {
+        float g = dy[r * lddy + c0];
+        if (y && !(y[r * ldy + c0] > 0.f)) g = 0.f;
+        const float v = (float)(A[0] * (double)g + (B[0] * ((double)h[r * ldh + c0] - mu[0]) + C[0]));
+        dx[r * lddx + c0] = v;
+        amax = fmaxf(amax, fabsf(v));
+      }
+    }
+  }
+  if (dx_absmax) {                                       // (an integer maximum of the bit patterns of non-negative floats: any order, same result)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    if (lane == 0)
+      atomicMax((unsigned int*)dx_absmax + (((blockIdx.y * gridDim.x + blockIdx.x) * 16 + wave) & (RGNN_BOUND_SLOTS - 1)), __float_as_uint(amax));
+  }
+}
+
+// d gamma = sum_s S2, d beta = sum_s S1: a thread per channel walks the segments in segment order (float64)
+__global__ __launch_bounds__(64) void k_bn_seg_bwd_params(const double* __restrict__ seg_bsums, int64_t n_seg, int n,
+                                                         float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= n) return;
+  double b = 0.0, g = 0.0;
+  for (int64_t f = 0; f < n_seg; f++) { b += seg_bsums[(f * 2 + 0) * n + c]; g += seg_bsums[(f * 2 + 1) * n + c]; }
+  if (dgamma) dgamma[c] = (float)g;
+  if (dbeta) dbeta[c] = (float)b;
+}
+
+}  // namespace
+
+extern "C" int rgnn_bn_segments_bwd(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* h, int64_t ldh,
+                                    const int64_t* seg_ptr, int64_t n_seg, int64_t m, int32_t n, const double* seg_stats,
+                                    const float* gamma, float eps, double* seg_bsums, float* dx, int64_t lddx, float* dgamma,
+                                    float* dbeta, float* dx_absmax, rgnn_stream_t stream) {
+  RGNN_CHECK_ARG(n >= 1 && n_seg >= 0 && m >= 0, "bad sizes");
+  RGNN_CHECK_ARG(n_seg < 65536 * 32, "too many segments");
+  RGNN_CHECK_ARG(n_seg == 0 || (seg_ptr && seg_stats && seg_bsums), "null pointers");
+  RGNN_CHECK_ARG(n_seg == 0 || m == 0 || (dy && h && dx), "null pointers");
+  RGNN_CHECK_ARG(lddy >= 0 && ldy >= 0 && ldh >= 0 && lddx >= 0, "negative leading dimension");
+  hipStream_t s = (hipStream_t)stream;
+  if (n_seg > 0) {
+    const dim3 grid((unsigned)n_seg, (unsigned)((n + 63) / 64));
+    const bool vec = (n & 3) == 0 && ((lddy | ldh | lddx | (y ? ldy : 0)) & 3) == 0 &&
+                     (((uintptr_t)dy | (uintptr_t)h | (uintptr_t)dx | (uintptr_t)y) & 15) == 0;
+    if (vec)
+      hipLaunchKernelGGL(k_bn_seg_bwd<4>, grid, dim3(1024), 0, s, dy, lddy, y, ldy, h, ldh, seg_ptr, m, n, seg_stats, gamma, eps,
+                         seg_bsums, dx, lddx, dx_absmax);
+    else
+      hipLaunchKernelGGL(k_bn_seg_bwd<1>, grid, dim3(1024), 0, s, dy, lddy, y, ldy, h, ldh, seg_ptr, m, n, seg_stats, gamma, eps,
+                         seg_bsums, dx, lddx, dx_absmax);
+  }
+  if (dgamma || dbeta)
+    hipLaunchKernelGGL(k_bn_seg_bwd_params, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, seg_bsums, n_seg, n, dgamma, dbeta);
+  RGNN_CHECK_LAUNCH();
+  return RGNN_OK;
+}

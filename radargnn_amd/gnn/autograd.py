@@ -10,6 +10,8 @@ Each ``torch.autograd.Function`` runs the same forward kernel as inference and a
                     edges, fused edge kernel) with a hand-scheduled backward over the same row lists;
 * ``BatchNormActFn`` train-mode BatchNorm1d (+ReLU) from the column statistics of the GEMM epilogue
                     (rgnn_bn_bwd_stats / rgnn_bn_bwd_apply; the [C]-sized coefficient algebra in float64 torch ops);
+* ``BatchNormSegmentsFn`` the same with statistics per segment of rows (``frame_scope``: one segment per loader batch of a grouped
+                    training step): rgnn_batchnorm_act_segments / rgnn_bn_segments_bwd;
 * ``AggregateFn``   M[t] = aggr_e(Q[s_e] + W_e a_e): rgnn_mpnn_aggregate / rgnn_mpnn_aggregate_bwd.
 
 The weight folds of the inference path (edge encoder, edge-embedding tail) are differentiable products of [D, De]-sized
@@ -315,6 +317,40 @@ def batch_norm_act(h, bn_module, stats=None, relu=False):
     if bn_module.empty_or_single(h.shape[0], h.shape[1]):       # (no rows: torch passes the empty matrix through; one row: an error)
         return torch.relu(h) if relu else h
     return BatchNormActFn.apply(h, mod.weight, mod.bias, stats, bn_module, relu)
+
+
+class BatchNormSegmentsFn(torch.autograd.Function):
+    """y = act(BatchNorm1d(h)) with batch statistics PER SEGMENT of rows (gnn.linear.frame_scope): every loader batch of a grouped
+    training step is normalised with its own statistics.  Forward: the fused two-launch form (rgnn_batchnorm_act_segments), which
+    leaves the exact per-segment mean and variance behind; backward: rgnn_bn_segments_bwd from those."""
+
+    @staticmethod
+    def forward(ctx, h, gamma, beta, seg_ptr, bn_module, relu: bool):
+        mod = bn_module.module
+        update = bn_module.training and mod.track_running_stats and not is_reexecution()   # (re-execution: already walked)
+        y, stats = ops.batchnorm_act_segments(h, seg_ptr, gamma, beta, mod.running_mean if update else None,
+                                              mod.running_var if update else None, mod.num_batches_tracked if update else None,
+                                              mod.momentum, mod.eps, relu, return_stats=True)
+        ctx.relu, ctx.eps = relu, mod.eps
+        ctx.pool = ops.ctx().bounds
+        ctx.affine = gamma is not None
+        ctx.save_for_backward(h, y if relu else None, gamma, seg_ptr, stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        h, y, gamma, seg_ptr, stats = ctx.saved_tensors
+        want = ctx.affine and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        with ops.using_bounds(ctx.pool):
+            dh, dgamma, dbeta = ops.batchnorm_segments_bwd(dy, y, h, seg_ptr, stats, gamma, ctx.eps, want_params=want)
+        return (dh if ctx.needs_input_grad[0] else None, dgamma if (ctx.affine and ctx.needs_input_grad[1]) else None,
+                dbeta if (ctx.affine and ctx.needs_input_grad[2]) else None, None, None, None)
+
+
+def batch_norm_act_segments(h, bn_module, seg_ptr, relu=False):
+    """The segment form of ``batch_norm_act``: statistics per segment ``[seg_ptr[s], seg_ptr[s + 1])`` of the rows of ``h``."""
+    mod = bn_module.module
+    return BatchNormSegmentsFn.apply(h, mod.weight, mod.bias, seg_ptr, bn_module, relu)
 
 
 class PermuteRowsFn(torch.autograd.Function):

@@ -130,13 +130,17 @@ class DetNetBasic(nn.Module):
         """-> (class logits [N, K], boxes [N, 4|5]); reference: gnn/gnn_models.py:104-134.
         ``frame_ptr`` (extension; int64 [F + 1], PyG ``Batch.ptr``): the batch holds F graphs laid back to back and every
         train-mode BatchNorm takes its statistics per graph -- the result of F single-graph forwards (how the reference runs
-        inference, evaluate.py:40) from one batched call.  Inference only."""
+        inference, evaluate.py:40) from one batched call.  With a recording active, or with ``x`` / ``edge_attr`` requiring a
+        gradient, the call records the differentiable segment-scoped forward (a grouped training step, gnn/trainer.py: one segment
+        per loader batch); in every other case the result is detached -- also when only the parameters require gradients."""
         graph = TargetCSR(edge_index, x.shape[0])
         if frame_ptr is not None:
             if AG.is_recording() or (torch.is_grad_enabled() and (x.requires_grad or edge_attr.requires_grad)):
-                # (ADVICE r03: silently detached outputs with updated running statistics are worse than an error)
-                raise NotImplementedError("per-frame BatchNorm statistics (frame_ptr) are an inference feature: call under "
-                                          "torch.no_grad() / with inputs that do not require gradients")
+                with frame_scope(frame_ptr.to(x.device), x.shape[0], graph):
+                    if AG.is_recording():
+                        return self.forward_graph(x, graph, graph.sort_edge_attr(edge_attr))
+                    with AG.recording(direct=True):
+                        return self.forward_graph(x, graph, graph.sort_edge_attr(edge_attr))
             with frame_scope(frame_ptr.to(x.device), x.shape[0], graph), torch.no_grad():
                 return self.forward_graph(x.detach(), graph, graph.sort_edge_attr(edge_attr.detach()))
 
@@ -246,7 +250,12 @@ class DetNetBasic(nn.Module):
             frames = _lin.current_frame_scope().padded_split()
         for conv, bn in zip(self.convs, self.batch_norms):
             use_batch = bn.training or bn.module.running_mean is None
-            if AG.is_recording():
+            if AG.is_recording() and bn.uses_frame_scope():
+                # statistics per segment while recording: the BatchNorm node takes them itself (AG.batch_norm_act_segments)
+                h, _ = conv.forward_sorted(x, graph, ea, want_stats=False, edge_tail=edge_tail)
+                with _rows_of("node"):
+                    x = bn.apply_frames(h, relu=True)
+            elif AG.is_recording():
                 h, stats = conv.forward_sorted(x, graph, ea, want_stats=use_batch, edge_tail=edge_tail)
                 x = AG.batch_norm_act(h, bn, stats=stats, relu=True)
             elif frames is not None:

@@ -205,15 +205,16 @@ class BatchNorm(nn.Module):
 
     def apply_frames(self, x: torch.Tensor, relu: bool) -> torch.Tensor:
         """act(BatchNorm(x)) with per-frame statistics (ops.batchnorm_segments); running statistics are updated frame after
-        frame, as a loop of single-frame forwards would."""
-        if AG.is_recording():
-            raise NotImplementedError("per-frame BatchNorm statistics (frame_scope) are an inference feature: no backward pass")
+        frame, as a loop of single-frame forwards would.  While a gradient is recorded (AG.is_recording()) the differentiable node
+        of the same launches (AG.batch_norm_act_segments)."""
         if x.shape[0] == 0 and self.empty_or_single(0, x.shape[1]):
             return torch.relu(x) if relu else x
         mod = self.module
         if mod.momentum is None:
             raise NotImplementedError("cumulative-moving-average BatchNorm (momentum=None) is not supported")
         seg = current_frame_scope().seg_ptr_for(x.shape[0])
+        if AG.is_recording():
+            return AG.batch_norm_act_segments(x, self, seg, relu=relu)
         d = lambda t: None if t is None else t.detach()
         update = self.training and mod.track_running_stats and not AG.is_reexecution()
         if os.environ.get("RGNN_BN_SEG_SPLIT") is not None:     # (the three-launch form: statistics, finish, apply)
@@ -308,7 +309,8 @@ def _run_mlp_grad(mods, x, a2, residual, want_stats, last_linear):
             fuse_relu = isinstance(nxt, nn.ReLU)
             fuse_bn = isinstance(nxt, BatchNorm)
             res = residual if is_last else None
-            need_stats = (fuse_bn and (nxt.training or nxt.module.running_mean is None)) or (is_last and want_stats)
+            per_frame = fuse_bn and nxt.uses_frame_scope()        # (statistics per segment: taken by the BatchNorm node itself)
+            need_stats = (fuse_bn and not per_frame and (nxt.training or nxt.module.running_mean is None)) or (is_last and want_stats)
             out = AG.linear(x, m_.weight, m_.bias, a2=a2, relu=fuse_relu and res is None, want_stats=need_stats,
                             residual=res)
             a2 = None
@@ -324,7 +326,7 @@ def _run_mlp_grad(mods, x, a2, residual, want_stats, last_linear):
                 i += 1
             elif fuse_bn:
                 relu_after = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-                x = AG.batch_norm_act(x, nxt, stats=st, relu=relu_after)
+                x = nxt.apply_frames(x, relu_after) if per_frame else AG.batch_norm_act(x, nxt, stats=st, relu=relu_after)
                 i += 2 if relu_after else 1
         elif isinstance(m_, nn.ReLU):
             x = torch.relu(x)

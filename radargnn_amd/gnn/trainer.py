@@ -26,14 +26,19 @@ import random
 import re
 import time
 from dataclasses import asdict
+from typing import List
 
 import numpy as np
 import torch
 from torch.optim.lr_scheduler import ExponentialLR, LambdaLR, ReduceLROnPlateau
 
 from .. import ops
+from ..data import DataLoader
+from ..inference import plan_steps
 from ..optim import FusedAdam
+from . import autograd as AG
 from .configs import GNNArchitectureConfig, TrainingConfig
+from .losses import detection_loss_groups
 
 # detections per class in RadarScenes (label order of the dataset: car, pedestrian, pedestrian group, two wheeler, large vehicle,
 # background), as published with the dataset and used by the reference's ClassDistribution
@@ -74,8 +79,48 @@ class _BatchLoss(torch.autograd.Function):
         return d_cls, d_bb, None, None, None, None, None
 
 
+def plan_train_steps(n_batches: int, batches_per_step: int) -> List[List[int]]:
+    """Loader batches (by index, in order) grouped into training steps of ``batches_per_step`` consecutive batches; the last step
+    of an epoch takes what is left."""
+    k = int(batches_per_step)
+    if k < 1:
+        raise ValueError("train_batches_per_step must be a positive integer")
+    n = int(n_batches)
+    return [list(range(i, min(i + k, n))) for i in range(0, n, k)]
+
+
+class _Step:
+    """Several consecutive loader batches collated into one disconnected graph; ``ptr``: int64 [G + 1] on the device, the node
+    offsets of the G loader batches (the segments of BatchNorm and the groups of the loss)."""
+    __slots__ = ("x", "edge_index", "edge_attr", "y", "ptr", "groups")
+
+    def __init__(self, x, edge_index, edge_attr, y, ptr, groups):
+        self.x, self.edge_index, self.edge_attr, self.y, self.ptr, self.groups = x, edge_index, edge_attr, y, ptr, groups
+
+
 class Trainer:
-    def __init__(self, config: TrainingConfig, model: torch.nn.Module):
+    """``Trainer(config, model)`` is the reference's trainer: one forward per loader batch, and for training one backward and one
+    optimizer step per loader batch.  Two keyword arguments let a step take several loader batches through ONE launch chain; every
+    train-mode BatchNorm then normalises each loader batch with its own statistics (``model(..., frame_ptr=<loader-batch borders>)``)
+    and the loss is computed per loader batch (``detection_loss(..., group_ptr=...)``).
+
+    ``valid_graphs_per_step`` > 0: validation groups whole consecutive loader batches until a step holds at least that many graphs
+    (``inference.plan_steps``).  It computes THE REFERENCE'S NUMBERS: every loader batch is normalised and scored on its own, the
+    running statistics are walked batch after batch, the epoch value is still the sum of the per-batch losses over ``len(loader)``.
+
+    ``train_batches_per_step`` = k > 1: a training step takes k consecutive loader batches (the last step of an epoch what is
+    left), backpropagates the MEAN of their k losses and makes one optimizer step.  This is GRADIENT ACCUMULATION: k times fewer
+    optimizer steps per epoch and a trajectory that differs from the reference's (equal only in the per-batch forward and loss).
+    The reported per-epoch figures stay means per loader batch."""
+
+    def __init__(self, config: TrainingConfig, model: torch.nn.Module, *, valid_graphs_per_step: int = 0,
+                 train_batches_per_step: int = 1):
+        for name, value, low in (("valid_graphs_per_step", valid_graphs_per_step, 0), ("train_batches_per_step", train_batches_per_step, 1)):
+            if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < low:
+                raise ValueError(f"{name} must be an integer >= {low}, got {value!r}")
+        self.valid_graphs_per_step = int(valid_graphs_per_step)
+        self.train_batches_per_step = int(train_batches_per_step)
+        self._mean_coef = {}                       # G -> device float [G] of 1 / G (the loss backward's per-group coefficients)
         self.config = config
         self.model = model
         self.train_loss_cls = []
@@ -172,7 +217,95 @@ class Trainer:
         return _BatchLoss.apply(cls, bb, y, class_weight, int(self.config.bg_index), float(self.config.cls_loss_weight),
                                 float(self.config.bb_loss_weight))
 
+    # ---- grouped steps: several loader batches per launch chain ------------------------------------------------------------------
+    def _steps(self, loader, device, plan, full):
+        """The loader's batches grouped into steps -> _Step per step (a step of one loader batch comes as the batch itself).
+        A resident ``radargnn_amd.data.DataLoader`` is planned up front (``plan(batch sizes) -> lists of batch indices``) and every
+        step collated ONCE from the store; any other iterable is walked, ``full(batches held, graphs held)`` closing a step, and
+        its batches concatenated on the device with offset ``edge_index``."""
+        if isinstance(loader, DataLoader):
+            store = loader.store
+            batch_ids = [np.asarray(ids, dtype=np.int64) for ids in loader.batch_ids()]     # ONE draw of a shuffling loader
+            steps = plan([ids.size for ids in batch_ids])
+            sizes = store.node_ptr[1:] - store.node_ptr[:-1]
+            bounds = np.concatenate(([0], np.cumsum([int(sizes[ids].sum()) for ids in batch_ids], dtype=np.int64))).astype(np.int64)
+            tabs = [bounds[s[0]:s[-1] + 2] - bounds[s[0]] for s in steps]                   # every step's borders in one upload
+            tab_at = np.concatenate(([0], np.cumsum([t.size for t in tabs]))).astype(np.int64)
+            tab_dev = torch.from_numpy(np.concatenate(tabs)).to(store.device) if tabs else None
+            for k, step in enumerate(steps):
+                batch = store.collate(np.concatenate([batch_ids[i] for i in step]))
+                if len(step) == 1:
+                    yield batch
+                else:
+                    yield _Step(batch.x, batch.edge_index, batch.edge_attr, batch.y, tab_dev[tab_at[k]:tab_at[k + 1]], len(step))
+            return
+        held, graphs = [], 0
+        for batch in loader:
+            if getattr(batch.x, "device", device) != device:
+                batch = batch.to(device)
+            held.append(batch)
+            graphs += int(getattr(batch, "num_graphs", 1))
+            if full(len(held), graphs):
+                yield self._concatenate(held, device)
+                held, graphs = [], 0
+        if held:
+            yield self._concatenate(held, device)
+
+    @staticmethod
+    def _concatenate(batches, device):
+        if len(batches) == 1:
+            return batches[0]
+        offsets = np.concatenate(([0], np.cumsum([b.x.shape[0] for b in batches], dtype=np.int64))).astype(np.int64)
+        return _Step(torch.cat([b.x for b in batches]),
+                     torch.cat([b.edge_index + int(o) for b, o in zip(batches, offsets)], dim=1),
+                     torch.cat([b.edge_attr for b in batches]), torch.cat([b.y for b in batches]),
+                     torch.from_numpy(offsets).to(device), len(batches))
+
+    def _step_loss(self, step: _Step, class_weight, record: bool):
+        """forward + loss of a grouped step -> (loss [G], out [G, 3] = loss, loss_cls, loss_bb per loader batch, sums [G, 4])"""
+        y = step.y
+        if self.config.adapt_orientation_angle:
+            y = ops.adapt_orientation_angle(y)
+        if record:                                         # the differentiable segment-scoped forward, recorded once
+            with AG.recording(direct=True):
+                cls, bb = self.model(step.x, step.edge_index, step.edge_attr, frame_ptr=step.ptr)
+        else:
+            cls, bb = self.model(step.x, step.edge_index, step.edge_attr, frame_ptr=step.ptr)
+        if y.dtype != torch.float32:
+            y = y.float()
+        loss, _, _, sums, out = detection_loss_groups(cls, bb, y, class_weight, step.ptr, int(self.config.bg_index), 1.0,
+                                                      float(self.config.cls_loss_weight), float(self.config.bb_loss_weight))
+        return loss, out, sums
+
+    def _train_epoch_grouped(self, loader, device, optimizer, class_weight):
+        """Gradient accumulation over ``train_batches_per_step`` loader batches: one forward, one loss launch, one backward launch of
+        the loss with the coefficients 1 / G, one optimizer step."""
+        acc = torch.zeros(4, dtype=torch.float64, device=device)       # sums of loss, loss_cls, loss_bb | NaN batches
+        k = self.train_batches_per_step
+        for step in self._steps(loader, device, lambda sizes: plan_train_steps(len(sizes), k), lambda held, _graphs: held >= k):
+            optimizer.zero_grad()
+            if not isinstance(step, _Step):                # one loader batch left: the step of the ungrouped loop
+                loss, out, sums = self._batch_loss(step, device, class_weight)
+                loss.backward()
+                optimizer.step()
+                acc[:3].add_(out)
+                acc[3:].add_(torch.isnan(sums[2:3]))
+                continue
+            loss, out, sums = self._step_loss(step, class_weight, record=True)
+            coef = self._mean_coef.get((device, step.groups))
+            if coef is None:
+                coef = self._mean_coef[(device, step.groups)] = torch.full((step.groups,), 1.0 / step.groups, dtype=torch.float32, device=device)
+            torch.autograd.backward([loss], [coef])        # d (1/G) sum_g loss_g: the loss kernel takes the coefficients per group
+            optimizer.step()
+            acc[:3].add_(out.sum(0))
+            acc[3:].add_(torch.isnan(sums[:, 2]).sum())
+        total, cls_sum, bb_sum, nan_batches = acc.tolist()                 # the epoch's one host read
+        n = len(loader)
+        return total / n, cls_sum / n, bb_sum / n, int(nan_batches)
+
     def _train_epoch(self, loader, device, optimizer, class_weight):
+        if self.train_batches_per_step > 1:
+            return self._train_epoch_grouped(loader, device, optimizer, class_weight)
         acc = torch.zeros(4, dtype=torch.float64, device=device)       # sums of loss, loss_cls, loss_bb | NaN batches
         for batch in loader:
             optimizer.zero_grad()
@@ -188,7 +321,16 @@ class Trainer:
     @torch.no_grad()
     def _validate_epoch(self, loader, device, class_weight) -> float:
         acc = torch.zeros(3, dtype=torch.float64, device=device)
-        for batch in loader:                               # the model stays in train mode, as in the reference
+        if self.valid_graphs_per_step > 0:
+            # whole consecutive loader batches per launch chain; each is still normalised and scored on its own (frame_ptr, group_ptr)
+            per_step = self.valid_graphs_per_step
+            for step in self._steps(loader, device, lambda sizes: plan_steps(sizes, per_step), lambda _held, graphs: graphs >= per_step):
+                if isinstance(step, _Step):
+                    acc.add_(self._step_loss(step, class_weight, record=False)[1].sum(0))
+                else:
+                    acc.add_(self._batch_loss(step, device, class_weight)[1])
+            return acc[0].item() / len(loader)
+        for batch in loader:                              # the model stays in train mode, as in the reference
             _, out, _ = self._batch_loss(batch, device, class_weight)
             acc.add_(out)
         return acc[0].item() / len(loader)

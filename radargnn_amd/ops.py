@@ -1269,9 +1269,11 @@ def batchnorm_segments_from_panels(stats_a: torch.Tensor, start_a: torch.Tensor,
 
 
 def batchnorm_act_segments(x: torch.Tensor, seg_ptr: torch.Tensor, gamma, beta, running_mean, running_var, num_batches_tracked,
-                           momentum: float, eps: float, relu: bool) -> torch.Tensor:
+                           momentum: float, eps: float, relu: bool, return_stats: bool = False):
     """act(BatchNorm(x)) with statistics per segment of rows: ``scale_shift_act_segments(x, batchnorm_segments(x, ...))`` in two
-    launches instead of three (rgnn_batchnorm_act_segments); the bound of the result travels with it."""
+    launches instead of three (rgnn_batchnorm_act_segments); the bound of the result travels with it.  ``return_stats``: also the
+    exact per-segment statistics the launches leave behind, float64 [F, 2, C] = (mean, unbiased variance), for
+    ``batchnorm_segments_bwd``."""
     x = _rowmajor(_dev(x, "x", torch.float32), "x")
     _dev(seg_ptr, "seg_ptr", torch.int64)
     m, n = x.shape
@@ -1286,7 +1288,40 @@ def batchnorm_act_segments(x: torch.Tensor, seg_ptr: torch.Tensor, gamma, beta, 
                                           float(eps), 1 if relu else 0, _ptr(sums), _ptr(table), _ptr(out), _ld(out),
                                           _ptr(in_bound) if out_bound is not None else None, _ptr(out_bound), _stream()))
     set_bound(out, out_bound)
-    return out
+    return (out, sums) if return_stats else out
+
+
+def batchnorm_segments_bwd(dy: torch.Tensor, y: Optional[torch.Tensor], h: torch.Tensor, seg_ptr: torch.Tensor,
+                           seg_stats: torch.Tensor, gamma: Optional[torch.Tensor], eps: float, want_params: bool = True):
+    """Backward of ``batchnorm_act_segments`` / ``batchnorm_segments`` + ``scale_shift_act_segments`` -> (dh [M, C], d gamma [C],
+    d beta [C]) (rgnn_bn_segments_bwd: two launches, float64 sums in a fixed order).  ``y``: the saved output when a ReLU was
+    fused, else None; ``h``: the layer's input; ``seg_stats``: what ``batchnorm_act_segments(..., return_stats=True)`` returned.
+    Inside a bound pool ``dh`` carries max |dh| for the f16x2 form of the dgrad launches that read it.  Rows outside every segment
+    are not written."""
+    dy = _rowmajor(_dev(dy, "dy", torch.float32), "dy")
+    h = _rowmajor(_dev(h, "h", torch.float32), "h")
+    if y is not None:
+        y = _rowmajor(_dev(y, "y", torch.float32), "y")
+    _dev(seg_ptr, "seg_ptr", torch.int64)
+    _dev(seg_stats, "seg_stats", torch.float64)
+    m, n = h.shape
+    f = seg_ptr.numel() - 1
+    if dy.shape != h.shape or (y is not None and y.shape != h.shape):
+        raise ValueError("batchnorm_segments_bwd: dy, y and h must have the same shape")
+    if f < 0 or tuple(seg_stats.shape) != (f, 2, n) or not seg_stats.is_contiguous():
+        raise ValueError("batchnorm_segments_bwd: seg_stats must be a contiguous float64 [segments, 2, C] tensor")
+    if gamma is not None:
+        gamma = _dev(gamma, "gamma", torch.float32).contiguous()
+    dx = torch.empty((m, n), dtype=torch.float32, device=h.device)
+    bsums = torch.empty((f, 2, n), dtype=torch.float64, device=h.device)
+    dgamma = torch.empty(n, dtype=torch.float32, device=h.device) if want_params else None
+    dbeta = torch.empty(n, dtype=torch.float32, device=h.device) if want_params else None
+    word = ctx().bounds.word() if ctx().bounds is not None else None
+    check(lib.rgnn_bn_segments_bwd(_ptr(dy), _ld(dy), _ptr(y), 0 if y is None else _ld(y), _ptr(h), _ld(h),
+                                   _ptr(seg_ptr.contiguous()), f, m, n, _ptr(seg_stats), _ptr(gamma), float(eps), _ptr(bsums),
+                                   _ptr(dx), n, _ptr(dgamma), _ptr(dbeta), _ptr(word), _stream()))
+    set_bound(dx, word)
+    return dx, dgamma, dbeta
 
 
 def scale_shift_act_segments(x: torch.Tensor, table: torch.Tensor, seg_ptr: torch.Tensor, relu: bool) -> torch.Tensor:
@@ -2313,8 +2348,11 @@ def confusion_matrix(y_true: torch.Tensor, y_pred: torch.Tensor, num_classes: in
 
 # ---- detection loss (csrc/loss.hip) ----------------------------------------------------------------------------------
 def detection_loss(cls: torch.Tensor, boxes: torch.Tensor, y: torch.Tensor, class_weight: Optional[torch.Tensor],
-                   bg_index: int, delta: float, cls_loss_weight: float, bb_loss_weight: float):
-    """-> (out f32 [3] = loss, loss_cls, loss_bb; sums f64 [4] for the backward pass) (rgnn_detection_loss)."""
+                   bg_index: int, delta: float, cls_loss_weight: float, bb_loss_weight: float,
+                   group_ptr: Optional[torch.Tensor] = None):
+    """-> (out f32 [3] = loss, loss_cls, loss_bb; sums f64 [4] for the backward pass) (rgnn_detection_loss).
+    ``group_ptr`` (int64 [G + 1] on the device): one result per group of rows [group_ptr[g], group_ptr[g + 1]) -> (out f32 [G, 3],
+    sums f64 [G, 4]) in one launch (rgnn_detection_loss_segments)."""
     cls = _rowmajor(_dev(cls, "cls", torch.float32), "cls")
     boxes = _rowmajor(_dev(boxes, "boxes", torch.float32), "boxes")
     y = _rowmajor(_dev(y, "y", torch.float32), "y")
@@ -2326,6 +2364,15 @@ def detection_loss(cls: torch.Tensor, boxes: torch.Tensor, y: torch.Tensor, clas
         _dev(class_weight, "class_weight", torch.float32)
         if class_weight.numel() != k or not class_weight.is_contiguous():
             raise ValueError("class_weight must be a contiguous [K] tensor")
+    if group_ptr is not None:
+        g = _group_count(group_ptr)
+        sums = torch.empty((g, 4), dtype=torch.float64, device=cls.device)
+        out = torch.empty((g, 3), dtype=torch.float32, device=cls.device)
+        check(lib.rgnn_detection_loss_segments(_ptr(cls), _ld(cls) if n > 1 else k, k, _ptr(boxes), _ld(boxes) if n > 1 else w, w,
+                                               _ptr(y), _ld(y) if n > 1 else 1 + w, _ptr(class_weight), n, _ptr(group_ptr), g,
+                                               int(bg_index), float(delta), float(cls_loss_weight), float(bb_loss_weight),
+                                               _ptr(sums), _ptr(out), _stream()))
+        return out, sums
     nb = int(lib.rgnn_detection_loss_blocks(n))
     partial = torch.empty(4 * nb, dtype=torch.float64, device=cls.device)
     sums = torch.empty(4, dtype=torch.float64, device=cls.device)
@@ -2336,12 +2383,34 @@ def detection_loss(cls: torch.Tensor, boxes: torch.Tensor, y: torch.Tensor, clas
     return out, sums
 
 
-def detection_loss_bwd(cls, boxes, y, class_weight, bg_index, delta, cls_loss_weight, bb_loss_weight, sums, grad_loss):
+def _group_count(group_ptr: torch.Tensor) -> int:
+    _dev(group_ptr, "group_ptr", torch.int64)
+    if group_ptr.dim() != 1 or group_ptr.numel() < 1 or not group_ptr.is_contiguous():
+        raise ValueError("group_ptr must be a contiguous int64 [G + 1] tensor")
+    return group_ptr.numel() - 1
+
+
+def detection_loss_bwd(cls, boxes, y, class_weight, bg_index, delta, cls_loss_weight, bb_loss_weight, sums, grad_loss,
+                       group_ptr: Optional[torch.Tensor] = None):
+    """-> (d cls, d boxes) of ``grad_loss * loss``; with ``group_ptr`` of ``sum_g grad_loss[g] * loss_g`` (``grad_loss`` float [G] on
+    the device, None = ones; rgnn_detection_loss_segments_bwd)."""
     cls = _rowmajor(cls, "cls"); boxes = _rowmajor(boxes, "boxes"); y = _rowmajor(y, "y")
     n, k = cls.shape
     w = boxes.shape[1]
     d_cls = torch.empty((n, k), dtype=torch.float32, device=cls.device)
     d_bb = torch.empty((n, w), dtype=torch.float32, device=cls.device)
+    if group_ptr is not None:
+        ng = _group_count(group_ptr)
+        if ng == 0:
+            return d_cls.zero_(), d_bb.zero_()
+        coef = None if grad_loss is None else grad_loss.reshape(-1).to(torch.float32).contiguous()
+        if coef is not None and coef.numel() != ng:
+            raise ValueError("grad_loss must hold one value per group")
+        check(lib.rgnn_detection_loss_segments_bwd(_ptr(cls), _ld(cls) if n > 1 else k, k, _ptr(boxes), _ld(boxes) if n > 1 else w,
+                                                   w, _ptr(y), _ld(y) if n > 1 else 1 + w, _ptr(class_weight), n, _ptr(group_ptr),
+                                                   ng, int(bg_index), float(delta), float(cls_loss_weight), float(bb_loss_weight),
+                                                   _ptr(sums), _ptr(coef), _ptr(d_cls), k, _ptr(d_bb), w, _stream()))
+        return d_cls, d_bb
     g = None if grad_loss is None else grad_loss.reshape(1).to(torch.float32).contiguous()
     check(lib.rgnn_detection_loss_bwd(_ptr(cls), _ld(cls) if n > 1 else k, k, _ptr(boxes), _ld(boxes) if n > 1 else w, w,
                                       _ptr(y), _ld(y) if n > 1 else 1 + w, _ptr(class_weight), n, int(bg_index), float(delta),
