@@ -41,7 +41,9 @@ typedef void* rgnn_stream_t; /* hipStream_t */
 #define RGNN_STATUS_KNN_TOO_FEW_POINTS 1 /* a frame has n_f <= k: sklearn raises ValueError              */
 #define RGNN_STATUS_DOT_PRODUCT 2        /* graph_constructor/features.py:56,77,91 "Error in dot product" */
 #define RGNN_STATUS_TIME_INDEX_OVERFLOW 4 /* more distinct timestamps in a frame than the LDS table holds  */
-#define RGNN_STATUS_EDGE_COUNT_CHANGED 8 /* rgnn_radius_graph_fill with status: rowptr[n] != the n_edges the caller sized for */
+#define RGNN_STATUS_EDGE_COUNT_CHANGED 8 /* rgnn_radius_graph_fill / rgnn_radius_graph_rows with status, rgnn_radius_graph_rows_direct,
+                                          * rgnn_radius_rows_commit: rowptr[n] != the n_edges the caller sized for (rows_direct also:
+                                          * a row whose length is no longer the committed one) */
 #define RGNN_STATUS_NOT_SYMMETRIC 16     /* rgnn_csr_by_target_symmetric: an edge (s,t) without its twin (t,s)               */
 #define RGNN_STATUS_SPLITK_TIMEOUT 32    /* a dense launch gave up waiting for a partial tile of another work-group (see splitk_ws) */
 #define RGNN_STATUS_GT_OBJECT_TOO_LARGE 64   /* rgnn_create_gt_boxes: an object of more than rgnn_gt_object_cap() points; its rows are not written */
@@ -124,9 +126,11 @@ int rgnn_grid_order_offsets(int64_t n, int64_t n_frames, int32_t dim, int64_t* o
  * rgnn_radius_rows_commit keeps it (rowptr_committed[n] must equal n_edges).  ONE launch behind the grid build: a point's row is
  * searched once and, if it has the committed length, written in ascending order to col / edge_index (/ relative_position) at the
  * committed place; a row of another length keeps its previous contents and raises RGNN_STATUS_EDGE_COUNT_CHANGED in `status`
- * (the points changed under the captured graph).  Replaces, for those steps, rgnn_radius_graph_count + the scan +
+ * (the points changed under the captured graph).  If rowptr_committed[n] != n_edges -- what col / edge_index / relative_position /
+ * tmp were sized for -- the launch writes nothing at all and raises the same bit, like the guarded rgnn_radius_graph_rows.
+ * Replaces, for those steps, rgnn_radius_graph_count + the scan +
  * rgnn_radius_rows_commit + rgnn_radius_graph_rows; same rows, same order, same values.  tmp: int32 [n_edges] scratch (rows of more
- * than 512 neighbours).  Reference: graph.py:68-82 (radius_neighbors_graph + nonzero), graph.py:199-200 (relative_position). */
+ * than 128 neighbours).  Reference: graph.py:68-82 (radius_neighbors_graph + nonzero), graph.py:199-200 (relative_position). */
 int rgnn_radius_graph_rows_direct(const rgnn_grid* g, double r, const int32_t* rowptr_committed, int32_t* col, int64_t* edge_index,
                                   int64_t n_edges, int32_t* tmp, int32_t* status, float* relative_position, int32_t undirected,
                                   rgnn_stream_t stream);

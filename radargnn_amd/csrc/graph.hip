@@ -98,9 +98,76 @@ GridView make_view(void* ws, int64_t n, int64_t B, int dim) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// The rules of the grid, each stated once: every grid build (k_frame_grid + k_bin_*, k_grid_frame, k_grid_frame_reg) calls these,
+// so all of them put every point in the same cell and at the same place inside it.
+// ------------------------------------------------------------------------------------------------
+// The grid of a frame of nf points from its bounding box.  cell_base: the frame's first cell in the static cell table, cap: its
+// share of that table.  cell_size > 0: radius mode; else kNN mode with about pts_per_cell points per cell.
+__device__ __forceinline__ FrameGrid frame_grid_geometry(double xmin, double xmax, double ymin, double ymax, int64_t nf,
+                                                         int64_t cell_base, int64_t cap, double cell_size, double pts_per_cell) {
+  FrameGrid g;
+  g.n_pts = (int32_t)nf;
+  g.cell_base = (int32_t)cell_base;
+  if (nf == 0) {
+    g.x0 = 0; g.y0 = 0; g.h = 1; g.gx = 1; g.gy = 1;
+  } else {
+    const double ex = xmax - xmin, ey = ymax - ymin;
+    double h;
+    if (cell_size > 0) {
+      // radius mode: h slightly larger than r so that |dx| <= r implies |cell difference| <= 1 even
+      // after the rounding of (x - x0) / h
+      h = cell_size * (1.0 + 9.5367431640625e-07);
+    } else {
+      // kNN mode: about pts_per_cell points per cell over the bounding box
+      const double area = ex * ey;
+      if (area > 0) h = sqrt(area * pts_per_cell / (double)nf);
+      else if (ex + ey > 0) h = (ex + ey) * pts_per_cell / (double)nf;
+      else h = 1.0;
+      // cells that are much finer than the box are pointless
+      const double hmin = fmax(ex, ey) * 1e-6;
+      if (h < hmin) h = hmin;
+      if (!(h > 0)) h = 1.0;
+    }
+    int64_t gx, gy;
+    for (;;) {
+      gx = (int64_t)floor(ex / h) + 1;
+      gy = (int64_t)floor(ey / h) + 1;
+      if (((gx + 7) / 8) * ((gy + 7) / 8) * 64 <= cap) break;  // cells incl. the padding of partial 8x8 tiles
+      h *= 1.5;
+    }
+    g.x0 = xmin; g.y0 = ymin; g.h = h; g.gx = (int32_t)gx; g.gy = (int32_t)gy;
+  }
+  g.tx = (g.gx + 7) / 8;
+  g.pad_ = 0;
+  return g;
+}
+
+// The cell of a point of the frame (points on the box's far edges fall into the last cell row / column).
+__device__ __forceinline__ int cell_of_point(const FrameGrid& g, double x, double y) {
+  int cx = (int)floor((x - g.x0) / g.h);
+  int cy = (int)floor((y - g.y0) / g.h);
+  cx = min(max(cx, 0), g.gx - 1);
+  cy = min(max(cy, 0), g.gy - 1);
+  return cell_id(g, cx, cy);
+}
+
+// The place of point i among the points of its cell, which `list` holds at [s0, s1) in the order the atomics handed out (not
+// reproducible): s0 plus the number of them with a SMALLER index, so every cell is in ascending index order whatever the atomics
+// did.  A cell of more than GRID_ORDERED_CELL_MAX points keeps the point's arrival place: ranking by counting is quadratic in the
+// cell size (10^5 coincident points would be 10^10 reads); such a cell is a degenerate input, and its order is then the one thing
+// in the path that is not reproducible.
+constexpr int GRID_ORDERED_CELL_MAX = 2048;
+__device__ __forceinline__ int place_in_cell(const int32_t* list, int s0, int s1, int32_t i, int arrival) {
+  if (s1 - s0 > GRID_ORDERED_CELL_MAX) return arrival;
+  int p = s0;
+  for (int j = s0; j < s1; j++) p += list[j] < i ? 1 : 0;
+  return p;
+}
+
+// ------------------------------------------------------------------------------------------------
 // per-frame bounding box and grid geometry: one block per frame
 // ------------------------------------------------------------------------------------------------
-constexpr int FG_THREADS = 1024;   // (one block per frame: a 100 000-point frame took 198 us with 256 threads)
+constexpr int FG_THREADS = 1024;  // (one block per frame: a 100 000-point frame took 198 us with 256 threads)
 __global__ __launch_bounds__(FG_THREADS) void k_frame_grid(const double* __restrict__ X, int dim,
                                                    const int64_t* __restrict__ frame_ptr, FrameGrid* __restrict__ frames,
                                                    double cell_size, double pts_per_cell, int32_t* __restrict__ cell_count,
@@ -143,44 +210,9 @@ __global__ __launch_bounds__(FG_THREADS) void k_frame_grid(const double* __restr
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    FrameGrid g;
     const int64_t nf = end - beg;
-    g.n_pts = (int32_t)nf;
-    g.cell_base = (int32_t)(CELLS_PER_POINT * beg + CELLS_PER_FRAME * (int64_t)f);
-    const int64_t cap = CELLS_PER_POINT * nf + CELLS_PER_FRAME;
-    if (nf == 0) {
-      g.x0 = 0; g.y0 = 0; g.h = 1; g.gx = 1; g.gy = 1;
-    } else {
-      xmin = red[0][0]; xmax = red[1][0]; ymin = red[2][0]; ymax = red[3][0];
-      const double ex = xmax - xmin, ey = ymax - ymin;
-      double h;
-      if (cell_size > 0) {
-        // radius mode: h slightly larger than r so that |dx| <= r implies |cell difference| <= 1 even
-        // after the rounding of (x - x0) / h
-        h = cell_size * (1.0 + 9.5367431640625e-07);
-      } else {
-        // kNN mode: about pts_per_cell points per cell over the bounding box
-        const double area = ex * ey;
-        if (area > 0) h = sqrt(area * pts_per_cell / (double)nf);
-        else if (ex + ey > 0) h = (ex + ey) * pts_per_cell / (double)nf;
-        else h = 1.0;
-        // cells that are much finer than the box are pointless
-        const double hmin = fmax(ex, ey) * 1e-6;
-        if (h < hmin) h = hmin;
-        if (!(h > 0)) h = 1.0;
-      }
-      int64_t gx, gy;
-      for (;;) {
-        gx = (int64_t)floor(ex / h) + 1;
-        gy = (int64_t)floor(ey / h) + 1;
-        if (((gx + 7) / 8) * ((gy + 7) / 8) * 64 <= cap) break;  // cells incl. the padding of partial 8x8 tiles
-        h *= 1.5;
-      }
-      g.x0 = xmin; g.y0 = ymin; g.h = h; g.gx = (int32_t)gx; g.gy = (int32_t)gy;
-    }
-    g.tx = (g.gx + 7) / 8;
-    g.pad_ = 0;
-    frames[f] = g;
+    frames[f] = frame_grid_geometry(red[0][0], red[1][0], red[2][0], red[3][0], nf, CELLS_PER_POINT * beg + CELLS_PER_FRAME * (int64_t)f,
+                                    CELLS_PER_POINT * nf + CELLS_PER_FRAME, cell_size, pts_per_cell);
   }
 }
 
@@ -201,11 +233,7 @@ __global__ __launch_bounds__(256) void k_bin_count(const double* __restrict__ X,
   if (i >= n) return;
   const int f = find_frame(frame_ptr, n_frames, i);
   const FrameGrid g = frames[f];
-  int cx = (int)floor((X[i * dim] - g.x0) / g.h);
-  int cy = (int)floor((X[i * dim + 1] - g.y0) / g.h);
-  cx = min(max(cx, 0), g.gx - 1);
-  cy = min(max(cy, 0), g.gy - 1);
-  const int c = cell_id(g, cx, cy);
+  const int c = cell_of_point(g, X[i * dim], X[i * dim + 1]);
   point_cell[i] = c;
   point_frame[i] = f;
   atomicAdd(&cell_count[c], 1);
@@ -213,10 +241,7 @@ __global__ __launch_bounds__(256) void k_bin_count(const double* __restrict__ X,
 
 // Points into cell order, general path, in two launches: the atomics hand out the places of a cell in ARRIVAL order (not
 // reproducible), so they only fill a scratch list (sorted_cell, overwritten by the second launch); the second launch gives every
-// point its cell's start plus the number of points of the cell with a smaller index (see k_grid_frame).
-constexpr int GRID_ORDERED_CELL_MAX = 2048;   // cells with more points keep the atomics' arrival order: ranking by counting is quadratic
-                                              // in the cell size (10^5 coincident points would be 10^10 reads); such a cell is a degenerate
-                                              // input, and its order is then the one thing in the path that is not reproducible
+// point its place (place_in_cell).
 __global__ __launch_bounds__(256) void k_bin_scatter(int64_t n, const int32_t* __restrict__ point_cell, const int32_t* __restrict__ cell_start,
                                                     int32_t* __restrict__ cell_count, int32_t* __restrict__ scratch,
                                                     int32_t* __restrict__ point_rank) {
@@ -238,10 +263,7 @@ __global__ __launch_bounds__(256) void k_bin_place(const double* __restrict__ X,
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int c = point_cell[i];
-  const int s0 = cell_start[c], s1 = cell_start[c + 1];
-  int p = s0;
-  if (s1 - s0 > GRID_ORDERED_CELL_MAX) p = point_rank[i];
-  else for (int j = s0; j < s1; j++) p += scratch[j] < (int32_t)i ? 1 : 0;
+  const int p = place_in_cell(scratch, cell_start[c], cell_start[c + 1], (int32_t)i, point_rank[i]);
   sorted_idx[p] = (int32_t)i;
   point_rank[i] = p;
   sorted_frame[p] = point_frame[i];
@@ -261,9 +283,9 @@ __global__ __launch_bounds__(256) void k_bin_cells(int64_t n, const int32_t* __r
 // points a contiguous slice of the point arrays, so the scan is local: cell_start = frame_ptr[f] + local prefix -- no
 // device-wide scan, no second and third pass over all points (five launches before: k_frame_grid, k_bin_count, two scan
 // kernels, k_bin_fill; 48 us on the C2 batch, most of it launch latency of a dependent chain).  The histogram / cursors live
-// in LDS when the frame's cells fit (GF_LDS_CELLS), else in the global cell table.  Arithmetic (grid geometry, cell of a
-// point) is the code of k_frame_grid / k_bin_count: same cells, hence the same candidate sets; the points INSIDE a cell are
-// in ascending index order on either path (r05: reproducible from run to run).
+// in LDS when the frame's cells fit (GF_LDS_CELLS), else in the global cell table.  Grid geometry, cell of a point and place
+// inside the cell are the functions k_frame_grid / k_bin_count / k_bin_place call: same cells, hence the same candidate sets;
+// the points INSIDE a cell are in ascending index order on either path (r05: reproducible from run to run).
 // ------------------------------------------------------------------------------------------------
 constexpr int GF_THREADS = 1024;
 constexpr int GF_LDS_CELLS = 32 * 1024;            // 128 KB of LDS counters: frames of up to ~16 000 points
@@ -271,6 +293,49 @@ __device__ __forceinline__ double gf_shfl_xor(double v, int o) {
   int2 t = __builtin_bit_cast(int2, v);
   t.x = __shfl_xor(t.x, o, 64); t.y = __shfl_xor(t.y, o, 64);
   return __builtin_bit_cast(double, t);
+}
+// The bounding box of a block of GF_THREADS threads from every thread's running extrema: thread 0 holds it afterwards.
+__device__ __forceinline__ void gf_block_box(double& xmin, double& xmax, double& ymin, double& ymax, double (*red)[GF_THREADS / 64]) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    xmin = fmin(xmin, gf_shfl_xor(xmin, o)); xmax = fmax(xmax, gf_shfl_xor(xmax, o));
+    ymin = fmin(ymin, gf_shfl_xor(ymin, o)); ymax = fmax(ymax, gf_shfl_xor(ymax, o));
+  }
+  if (lane == 0) { red[0][w] = xmin; red[1][w] = xmax; red[2][w] = ymin; red[3][w] = ymax; }
+  __syncthreads();
+  if (t == 0) {
+    for (int i = 1; i < GF_THREADS / 64; i++) {
+      xmin = fmin(xmin, red[0][i]); xmax = fmax(xmax, red[1][i]); ymin = fmin(ymin, red[2][i]); ymax = fmax(ymax, red[3][i]);
+    }
+  }
+}
+// Exclusive scan over the block's counter table cnt[0, cells), thread t owning `per` consecutive cells.  The first place of cell c --
+// `first` plus the points of the cells before it -- goes to cell_start[c], to cnt[c] (the cursor of the fill phase) and, where
+// given, to first_place[c]; the cells of the frame's share of the table that its grid does not use, [cells, cap), start at `end`.
+__device__ __forceinline__ void gf_scan_cells(int32_t* cnt, int32_t* first_place, int32_t* cell_start, int cells, int64_t cap, int first,
+                                              int32_t end, int* wsum) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int per = (cells + GF_THREADS - 1) / GF_THREADS;
+  const int lo = min(t * per, cells), hi = min(lo + per, cells);
+  int sum = 0;
+  for (int c = lo; c < hi; c++) sum += cnt[c];
+  int inc = sum;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
+  if (lane == 63) wsum[w] = inc;
+  __syncthreads();
+  int before = 0;
+  for (int i = 0; i < w; i++) before += wsum[i];
+  int run = first + before + inc - sum;                              // global position of the first point of cell `lo`
+  for (int c = lo; c < hi; c++) {
+    const int k = cnt[c];
+    cnt[c] = run;
+    if (first_place) first_place[c] = run;
+    cell_start[c] = run;
+    run += k;
+  }
+  for (int64_t c = cells + t; c < cap; c += GF_THREADS) cell_start[c] = end;
 }
 template <int DIM>
 __device__ __forceinline__ void gf_block(const double* __restrict__ X, const int64_t* __restrict__ frame_ptr,
@@ -285,7 +350,7 @@ __device__ __forceinline__ void gf_block(const double* __restrict__ X, const int
   __shared__ double red[4][GF_THREADS / 64];
   __shared__ FrameGrid sg;
   __shared__ int wsum[GF_THREADS / 64];
-  const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int f = blockIdx.x, t = threadIdx.x;
   const int64_t beg = frame_ptr[f], end = frame_ptr[f + 1];
   const int64_t nf = end - beg;
   const int64_t c0 = CELLS_PER_POINT * beg + CELLS_PER_FRAME * (int64_t)f;
@@ -297,49 +362,10 @@ __device__ __forceinline__ void gf_block(const double* __restrict__ X, const int
     xmin = fmin(xmin, x); xmax = fmax(xmax, x);
     ymin = fmin(ymin, y); ymax = fmax(ymax, y);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    xmin = fmin(xmin, gf_shfl_xor(xmin, o)); xmax = fmax(xmax, gf_shfl_xor(xmax, o));
-    ymin = fmin(ymin, gf_shfl_xor(ymin, o)); ymax = fmax(ymax, gf_shfl_xor(ymax, o));
-  }
-  if (lane == 0) { red[0][w] = xmin; red[1][w] = xmax; red[2][w] = ymin; red[3][w] = ymax; }
-  __syncthreads();
+  gf_block_box(xmin, xmax, ymin, ymax, red);
   if (t == 0) {
-    for (int i = 1; i < GF_THREADS / 64; i++) {
-      xmin = fmin(xmin, red[0][i]); xmax = fmax(xmax, red[1][i]); ymin = fmin(ymin, red[2][i]); ymax = fmax(ymax, red[3][i]);
-    }
-    FrameGrid g;
-    g.n_pts = (int32_t)nf;
-    g.cell_base = (int32_t)c0;
-    if (nf == 0) {
-      g.x0 = 0; g.y0 = 0; g.h = 1; g.gx = 1; g.gy = 1;
-    } else {                                            // (the geometry rules of k_frame_grid, word for word)
-      const double ex = xmax - xmin, ey = ymax - ymin;
-      double h;
-      if (cell_size > 0) {
-        h = cell_size * (1.0 + 9.5367431640625e-07);
-      } else {
-        const double area = ex * ey;
-        if (area > 0) h = sqrt(area * pts_per_cell / (double)nf);
-        else if (ex + ey > 0) h = (ex + ey) * pts_per_cell / (double)nf;
-        else h = 1.0;
-        const double hmin = fmax(ex, ey) * 1e-6;
-        if (h < hmin) h = hmin;
-        if (!(h > 0)) h = 1.0;
-      }
-      int64_t gx, gy;
-      for (;;) {
-        gx = (int64_t)floor(ex / h) + 1;
-        gy = (int64_t)floor(ey / h) + 1;
-        if (((gx + 7) / 8) * ((gy + 7) / 8) * 64 <= cap) break;
-        h *= 1.5;
-      }
-      g.x0 = xmin; g.y0 = ymin; g.h = h; g.gx = (int32_t)gx; g.gy = (int32_t)gy;
-    }
-    g.tx = (g.gx + 7) / 8;
-    g.pad_ = 0;
-    frames[f] = g;
-    sg = g;
+    sg = frame_grid_geometry(xmin, xmax, ymin, ymax, nf, c0, cap, cell_size, pts_per_cell);
+    frames[f] = sg;
     if (f == n_frames - 1) cell_start[n_cells] = (int32_t)end;     // end marker of the cell table
   }
   __syncthreads();
@@ -350,43 +376,19 @@ __device__ __forceinline__ void gf_block(const double* __restrict__ X, const int
   __syncthreads();
   // ---- cell of every point + histogram
   for (int64_t i = beg + t; i < end; i += GF_THREADS) {
-    int cx = (int)floor((X[i * DIM] - g.x0) / g.h);
-    int cy = (int)floor((X[i * DIM + 1] - g.y0) / g.h);
-    cx = min(max(cx, 0), g.gx - 1);
-    cy = min(max(cy, 0), g.gy - 1);
-    const int c = cell_id(g, cx, cy);
+    const int c = cell_of_point(g, X[i * DIM], X[i * DIM + 1]);
     point_cell[i] = c;
     point_frame[i] = f;
     atomicAdd(&cnt[c - g.cell_base], 1);
   }
   __syncthreads();
-  // ---- exclusive scan over the cells: thread t owns `per` consecutive cells
-  const int per = (cells + GF_THREADS - 1) / GF_THREADS;
-  const int lo = min(t * per, cells), hi = min(lo + per, cells);
-  int sum = 0;
-  for (int c = lo; c < hi; c++) sum += cnt[c];
-  int inc = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  int before = 0;
-  for (int i = 0; i < w; i++) before += wsum[i];
-  int run = (int)beg + before + inc - sum;                           // global position of the first point of cell `lo`
-  for (int c = lo; c < hi; c++) {
-    const int k = cnt[c];
-    cnt[c] = run;                                                    // cursor of the fill phase
-    cell_start[c0 + c] = run;
-    run += k;
-  }
-  for (int64_t c = cells + t; c < cap; c += GF_THREADS) cell_start[c0 + c] = (int32_t)end;   // cells the grid does not use
+  gf_scan_cells(cnt, nullptr, cell_start + c0, cells, cap, (int)beg, (int32_t)end, wsum);
   __syncthreads();
   // ---- points into cell order.  The atomics hand out the places of a cell in ARRIVAL order, which varies from run to run (and
   // with whatever else runs on the device); everything downstream follows the order of the points inside a cell -- the visiting
   // order of the conv layers, the window plan, which targets a window hands to the per-target kernel -- and with it the last bits of
   // the outputs (r05: two threads driving two models got results 1e-7 apart from the same calls alone, tests/test_gpu_threads.py).
-  // So the arrival order only fills a scratch list (sorted_cell, overwritten below); a point's place is its cell's start plus the
-  // number of points of the cell with a SMALLER index: ascending index inside every cell, whatever the atomics did.
+  // So the arrival order only fills a scratch list (sorted_cell, overwritten below) that place_in_cell ranks.
   for (int64_t i = beg + t; i < end; i += GF_THREADS) {
     const int c = point_cell[i];
     const int at = atomicAdd(&cnt[c - g.cell_base], 1);
@@ -395,11 +397,8 @@ __device__ __forceinline__ void gf_block(const double* __restrict__ X, const int
   }
   __syncthreads();
   for (int64_t i = beg + t; i < end; i += GF_THREADS) {
-    const int c = point_cell[i];
-    const int s0 = cell_start[c0 + (c - g.cell_base)], s1 = cnt[c - g.cell_base];      // (the cursor stands at the cell's end now)
-    int p = s0;
-    if (s1 - s0 > GRID_ORDERED_CELL_MAX) p = point_rank[i];
-    else for (int j = s0; j < s1; j++) p += sorted_cell[j] < (int32_t)i ? 1 : 0;
+    const int cl = point_cell[i] - g.cell_base;
+    const int p = place_in_cell(sorted_cell, cell_start[c0 + cl], cnt[cl], (int32_t)i, point_rank[i]);   // (the cursor stands at the cell's end now)
     sorted_idx[p] = (int32_t)i;
     point_rank[i] = p;
     sorted_frame[p] = f;
@@ -427,7 +426,7 @@ __global__ __launch_bounds__(GF_THREADS) void k_grid_frame(const double* __restr
 // thread keeps ITS points -- coordinates, cell, arrival place -- in registers from the first phase to the last, the arrival lists and
 // the cells' first places live in LDS beside the counters.  k_grid_frame reads every point's coordinates three times, its cell three
 // times and the arrival lists from global memory, a dependent round trip per phase (seven phases: 24 - 32 us per batch whatever the
-// frames hold); here global memory is read once and written once.  Same arithmetic, same cells, same order inside a cell: the
+// frames hold); here global memory is read once and written once.  The same functions give geometry, cell and place: the
 // outputs are identical.  A frame beyond the promise (more points than the registers hold, or more cells than the LDS table)
 // takes the general block code.
 constexpr int GFR_PPT = 4;
@@ -443,7 +442,7 @@ __global__ __launch_bounds__(GF_THREADS) void k_grid_frame_reg(const double* __r
   __shared__ double red[4][GF_THREADS / 64];
   __shared__ FrameGrid sg;
   __shared__ int wsum[GF_THREADS / 64];
-  const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int f = blockIdx.x, t = threadIdx.x;
   const int64_t beg = frame_ptr[f], end = frame_ptr[f + 1];
   const int64_t nf = end - beg;
   const int64_t c0 = CELLS_PER_POINT * beg + CELLS_PER_FRAME * (int64_t)f;
@@ -469,49 +468,10 @@ __global__ __launch_bounds__(GF_THREADS) void k_grid_frame_reg(const double* __r
       ymin = fmin(ymin, v.y); ymax = fmax(ymax, v.y);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    xmin = fmin(xmin, gf_shfl_xor(xmin, o)); xmax = fmax(xmax, gf_shfl_xor(xmax, o));
-    ymin = fmin(ymin, gf_shfl_xor(ymin, o)); ymax = fmax(ymax, gf_shfl_xor(ymax, o));
-  }
-  if (lane == 0) { red[0][w] = xmin; red[1][w] = xmax; red[2][w] = ymin; red[3][w] = ymax; }
-  __syncthreads();
+  gf_block_box(xmin, xmax, ymin, ymax, red);
   if (t == 0) {
-    for (int i = 1; i < GF_THREADS / 64; i++) {
-      xmin = fmin(xmin, red[0][i]); xmax = fmax(xmax, red[1][i]); ymin = fmin(ymin, red[2][i]); ymax = fmax(ymax, red[3][i]);
-    }
-    FrameGrid g;
-    g.n_pts = (int32_t)nf;
-    g.cell_base = (int32_t)c0;
-    if (nf == 0) {
-      g.x0 = 0; g.y0 = 0; g.h = 1; g.gx = 1; g.gy = 1;
-    } else {                                            // (the geometry rules of k_frame_grid / gf_block, word for word)
-      const double ex = xmax - xmin, ey = ymax - ymin;
-      double h;
-      if (cell_size > 0) {
-        h = cell_size * (1.0 + 9.5367431640625e-07);
-      } else {
-        const double area = ex * ey;
-        if (area > 0) h = sqrt(area * pts_per_cell / (double)nf);
-        else if (ex + ey > 0) h = (ex + ey) * pts_per_cell / (double)nf;
-        else h = 1.0;
-        const double hmin = fmax(ex, ey) * 1e-6;
-        if (h < hmin) h = hmin;
-        if (!(h > 0)) h = 1.0;
-      }
-      int64_t gx, gy;
-      for (;;) {
-        gx = (int64_t)floor(ex / h) + 1;
-        gy = (int64_t)floor(ey / h) + 1;
-        if (((gx + 7) / 8) * ((gy + 7) / 8) * 64 <= cap) break;
-        h *= 1.5;
-      }
-      g.x0 = xmin; g.y0 = ymin; g.h = h; g.gx = (int32_t)gx; g.gy = (int32_t)gy;
-    }
-    g.tx = (g.gx + 7) / 8;
-    g.pad_ = 0;
-    frames[f] = g;
-    sg = g;
+    sg = frame_grid_geometry(xmin, xmax, ymin, ymax, nf, c0, cap, cell_size, pts_per_cell);
+    frames[f] = sg;
     if (f == n_frames - 1) cell_start[n_cells] = (int32_t)end;     // end marker of the cell table
   }
   __syncthreads();
@@ -526,38 +486,14 @@ __global__ __launch_bounds__(GF_THREADS) void k_grid_frame_reg(const double* __r
     const int64_t i = beg + t + k * GF_THREADS;
     pc[k] = 0;
     if (i < end) {
-      int cx = (int)floor((px[k] - g.x0) / g.h);
-      int cy = (int)floor((py[k] - g.y0) / g.h);
-      cx = min(max(cx, 0), g.gx - 1);
-      cy = min(max(cy, 0), g.gy - 1);
-      pc[k] = cell_id(g, cx, cy);
+      pc[k] = cell_of_point(g, px[k], py[k]);
       point_cell[i] = pc[k];
       point_frame[i] = f;
       atomicAdd(&gf_cnt[pc[k] - g.cell_base], 1);
     }
   }
   __syncthreads();
-  // ---- exclusive scan over the cells: thread t owns `per` consecutive cells
-  const int per = (cells + GF_THREADS - 1) / GF_THREADS;
-  const int lo = min(t * per, cells), hi = min(lo + per, cells);
-  int sum = 0;
-  for (int c = lo; c < hi; c++) sum += gf_cnt[c];
-  int inc = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  int before = 0;
-  for (int i = 0; i < w; i++) before += wsum[i];
-  int run = (int)beg + before + inc - sum;                           // global position of the first point of cell `lo`
-  for (int c = lo; c < hi; c++) {
-    const int k = gf_cnt[c];
-    gf_cnt[c] = run;                                                 // cursor of the fill phase
-    cst[c] = run;
-    cell_start[c0 + c] = run;
-    run += k;
-  }
-  for (int64_t c = cells + t; c < cap; c += GF_THREADS) cell_start[c0 + c] = (int32_t)end;   // cells the grid does not use
+  gf_scan_cells(gf_cnt, cst, cell_start + c0, cells, cap, (int)beg, (int32_t)end, wsum);
   __syncthreads();
   // ---- arrival places (the atomics' order varies from run to run: it only fills the lists the ranking below reads)
   int at[GFR_PPT];
@@ -577,10 +513,8 @@ __global__ __launch_bounds__(GF_THREADS) void k_grid_frame_reg(const double* __r
     const int64_t i = beg + t + k * GF_THREADS;
     if (i < end) {
       const int cl = pc[k] - g.cell_base;
-      const int s0 = cst[cl], s1 = gf_cnt[cl];                       // (the cursor stands at the cell's end now)
-      int p = s0;
-      if (s1 - s0 > GRID_ORDERED_CELL_MAX) p = at[k];
-      else for (int j = s0; j < s1; j++) p += arr[j - (int)beg] < (int32_t)i ? 1 : 0;
+      // (the cursor stands at the cell's end now; the arrival lists are indexed from the frame's first point)
+      const int p = (int)beg + place_in_cell(arr, cst[cl] - (int)beg, gf_cnt[cl] - (int)beg, (int32_t)i, at[k] - (int)beg);
       sorted_idx[p] = (int32_t)i;
       point_rank[i] = p;
       sorted_frame[p] = f;
@@ -600,6 +534,39 @@ __device__ __forceinline__ double dist2(const double* __restrict__ q, const doub
   }
   return d2;
 }
+
+// One finished edge (i -> j) at position pos of the edge list, written the same way by every kernel that writes edges: the
+// neighbour in nbr (col of a radius graph, nbr of a kNN graph), both rows of edge_index [2, E] and the relative_position
+// attributes [E, 2] (each optional).
+struct EdgeWriter {
+  int32_t* nbr;
+  int64_t* edge_index;
+  int64_t E;
+  float* rel_pos;
+  int undirected;
+  __device__ __forceinline__ void ids(int64_t pos, int i, int j) const {
+    nbr[pos] = j;
+    if (edge_index) {
+      edge_index[pos] = i;                               // E[:,0] = query point (graph.py:61)
+      edge_index[E + pos] = j;                           // E[:,1] = neighbour   (graph.py:62)
+    }
+  }
+  __device__ __forceinline__ void attr(int64_t pos, double xi, double yi, double xj, double yj) const {
+    double dx = xi - xj, dy = yi - yj;                   // graph.py:199-200
+    if (undirected) { dx = fabs(dx); dy = fabs(dy); }
+    *(float2*)(rel_pos + pos * 2) = make_float2((float)dx, (float)dy);
+  }
+  // ... with its attributes, from the first two coordinates of both points (the float64 values of their rows of X)
+  __device__ __forceinline__ void edge(int64_t pos, int i, int j, double xi, double yi, double xj, double yj) const {
+    ids(pos, i, j);
+    if (rel_pos) attr(pos, xi, yi, xj, yj);
+  }
+  // ... the neighbour's coordinates one gather away at pj: read only when the attributes are wanted
+  __device__ __forceinline__ void edge(int64_t pos, int i, int j, double xi, double yi, const double* pj) const {
+    ids(pos, i, j);
+    if (rel_pos) attr(pos, xi, yi, pj[0], pj[1]);
+  }
+};
 
 // ------------------------------------------------------------------------------------------------
 // radius graph: count pass and fill pass share the traversal
@@ -730,10 +697,45 @@ __global__ __launch_bounds__(256) void k_rank_rows(const int32_t* __restrict__ r
 #pragma unroll
     for (int u = 0; u < 4; u++) rank += (b + u <= last && c[u] < v) ? 1 : 0;
   }
-  out[beg + rank] = v;
-  if (edge_index) {
-    edge_index[beg + rank] = i;            // E[:,0] = query point (graph.py:61)
-    edge_index[n_edges + beg + rank] = v;  // E[:,1] = neighbour   (graph.py:62)
+  EdgeWriter{out, edge_index, n_edges, nullptr, 0}.ids(beg + rank, i, v);
+}
+
+// The staged row of the two team fill kernels: a team of 16 lanes searches a dense row 16 candidates a trip, stages the hits -- in
+// LDS (`stg`) when the row fits there, else in the row's slice of the global scratch (`tmp_row`) -- and then ranks them.
+// One trip: the hits are appended in lane order behind the `cnt` staged so far, none beyond `cap` entries; -> the trip's hits.
+__device__ __forceinline__ int stage_hits(bool hit, int idx, int l, int cnt, int cap, bool in_lds, int32_t* stg, int32_t* tmp_row) {
+  const int team_shift = (threadIdx.x & 63) & ~15;       // this team's bits in a wave-wide ballot
+  const unsigned m = (unsigned)((__ballot(hit) >> team_shift) & 0xffffu);
+  if (hit) {
+    const int at = cnt + __popc(m & ((1u << l) - 1u));
+    if (at < cap) { if (in_lds) stg[at] = idx; else tmp_row[at] = idx; }
+  }
+  return __popc(m);
+}
+// The d staged ids are distinct, so the number of smaller ones is an entry's place in the ascending row: lane l ranks entries
+// l, l + 16, ... and hands each to emit(id, rank).
+template <class Emit>
+__device__ __forceinline__ void rank_staged_row(bool in_lds, const int32_t* stg, const int32_t* tmp_row, int d, int l, Emit emit) {
+  if (in_lds) {
+    // (the team's lanes are lanes of one wave: its LDS writes are ordered before the reads below by the wave's own program order
+    //  plus an LDS wait -- no block-wide barrier, which teams with other rows have already left)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_s_waitcnt(0xc07f);                   // lgkmcnt(0)
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (int c = l; c < d; c += 16) {
+      const int v = ((const volatile int32_t*)stg)[c];
+      int rank = 0;
+      for (int o = 0; o < d; o++) rank += (((const volatile int32_t*)stg)[o] < v) ? 1 : 0;
+      emit(v, rank);
+    }
+    return;
+  }
+  __threadfence();                                        // the staged row is read back by the other lanes of the team (L2)
+  for (int c = l; c < d; c += 16) {
+    const int v = __hip_atomic_load(tmp_row + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int rank = 0;
+    for (int o = 0; o < d; o++) rank += (__hip_atomic_load(tmp_row + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v) ? 1 : 0;
+    emit(v, rank);
   }
 }
 
@@ -767,19 +769,8 @@ __global__ __launch_bounds__(256) void k_radius_rows(int64_t n, const double* __
   double q[DIM];
 #pragma unroll
   for (int k = 0; k < DIM; k++) q[k] = X[i * DIM + k];
-  auto emit = [&](int v, int rank) {
-    const int64_t pos = (int64_t)beg + rank;
-    col[pos] = v;
-    if (edge_index) {
-      edge_index[pos] = i;                               // E[:,0] = query point (graph.py:61)
-      edge_index[n_edges + pos] = v;                     // E[:,1] = neighbour   (graph.py:62)
-    }
-    if (rel_pos) {
-      double dx = q[0] - X[(int64_t)v * DIM], dy = q[1] - X[(int64_t)v * DIM + 1];      // graph.py:199-200
-      if (rel_undirected) { dx = fabs(dx); dy = fabs(dy); }
-      *(float2*)(rel_pos + pos * 2) = make_float2((float)dx, (float)dy);
-    }
-  };
+  const EdgeWriter out{col, edge_index, n_edges, rel_pos, rel_undirected};
+  auto emit = [&](int v, int rank) { out.edge((int64_t)beg + rank, (int)i, v, q[0], q[1], X + (int64_t)v * DIM); };
   if (d <= RADIUS_CACHE) {
     constexpr int SLOTS = (RADIUS_CACHE + 15) / 16;
     int e[SLOTS], rk[SLOTS];
@@ -810,7 +801,6 @@ __global__ __launch_bounds__(256) void k_radius_rows(int64_t n, const double* __
   const FrameGrid g = frames[point_frame[i]];
   int cx, cy;
   cell_xy(g, point_cell[i], cx, cy);
-  const int team_shift = (threadIdx.x & 63) & ~15;       // this team's bits in a wave-wide ballot
   int cnt = 0;
   for (int u = 0; u < 9; u++) {
     const int xx = cx + (u % 3) - 1, yy = cy + (u / 3) - 1;
@@ -826,35 +816,10 @@ __global__ __launch_bounds__(256) void k_radius_rows(int64_t n, const double* __
         const double d2 = dist2<DIM>(q, sorted_pos + (int64_t)ps * DIM);
         hit = idx != (int)i && d2 <= r2;
       }
-      const unsigned m = (unsigned)((__ballot(hit) >> team_shift) & 0xffffu);
-      if (hit) {
-        const int at = cnt + __popc(m & ((1u << l) - 1u));
-        if (in_lds) stg[at] = idx; else tmp[beg + at] = idx;
-      }
-      cnt += __popc(m);
+      cnt += stage_hits(hit, idx, l, cnt, d, in_lds, stg, tmp + beg);
     }
   }
-  if (in_lds) {
-    // (the team's lanes are lanes of one wave: its LDS writes are ordered before the reads below by the wave's own program order
-    //  plus an LDS wait -- no block-wide barrier, which teams with cached rows have already left)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_s_waitcnt(0xc07f);                   // lgkmcnt(0)
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    for (int c = l; c < d; c += 16) {
-      const int v = ((volatile int32_t*)stg)[c];
-      int rank = 0;
-      for (int o = 0; o < d; o++) rank += (((volatile int32_t*)stg)[o] < v) ? 1 : 0;
-      emit(v, rank);
-    }
-    return;
-  }
-  __threadfence();                                        // the staged row is read back by the other lanes of the team (L2)
-  for (int c = l; c < d; c += 16) {
-    const int v = __hip_atomic_load(tmp + beg + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int rank = 0;
-    for (int o = 0; o < d; o++) rank += (__hip_atomic_load(tmp + beg + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v) ? 1 : 0;
-    emit(v, rank);
-  }
+  rank_staged_row(in_lds, stg, tmp + beg, d, l, emit);
 }
 
 // Search + fill in ONE launch for REPLAYED steps (r06, rgnn_radius_graph_rows_direct).  A captured step already knows the rows of its
@@ -863,7 +828,8 @@ __global__ __launch_bounds__(256) void k_radius_rows(int64_t n, const double* __
 // commit copy, no neighbour cache (k_radius + two scan kernels + k_rows_commit + k_radius_rows: five launches, ~94 us on the C2 batch).
 // A row of another length means the points changed under the captured graph: nothing of that row is written (the previous contents
 // stay, as with the guarded fill) and STATUS_EDGE_COUNT_CHANGED is raised -- per row, which is stricter than the total the guarded fill
-// compares.  The nine cell ranges are fetched in one round (lane u < 9 takes cell u) and walked as ONE list, sixteen candidates a trip.
+// compares; a committed total other than n_edges (what the buffers were sized for) refuses the whole launch, as it does there.
+// The nine cell ranges are fetched in one round (lane u < 9 takes cell u) and walked as ONE list, sixteen candidates a trip.
 template <int DIM>
 __global__ __launch_bounds__(256) void k_radius_rows_direct(int64_t n, const double* __restrict__ X,
                                                            const int32_t* __restrict__ point_cell, const int32_t* __restrict__ point_frame,
@@ -879,8 +845,10 @@ __global__ __launch_bounds__(256) void k_radius_rows_direct(int64_t n, const dou
   const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
   const int l = threadIdx.x & 15;
   if (i >= n) return;
-  if (i == 0 && l == 0 && (int64_t)rowptr[n] != n_edges) atomicOr(status, RGNN_STATUS_EDGE_COUNT_CHANGED);   // (the buffers were sized for n_edges)
   const int beg = rowptr[i], d = rowptr[i + 1] - beg;
+  // (the buffers were sized for n_edges: with another total the launch writes nothing, like the guarded k_radius_rows.  Uniform, and
+  //  requested WITH the row's bounds -- this kernel is a chain of dependent loads -- and first needed where the first hit is staged)
+  const bool stale = (int64_t)rowptr[n] != n_edges;
   int32_t* const stg = stage_lds[threadIdx.x >> 4];
   const bool in_lds = d <= ROWS_LDS_DIRECT;
   double q[DIM];
@@ -903,7 +871,7 @@ __global__ __launch_bounds__(256) void k_radius_rows_direct(int64_t n, const dou
 #pragma unroll
   for (int o = 1; o < 16; o <<= 1) { const int u = __shfl_up(incl, o, 16); if (l >= o) incl += u; }
   const int total = __shfl(incl, 15, 16);
-  const int team_shift = (threadIdx.x & 63) & ~15;       // this team's bits in a wave-wide ballot
+  const int cap = stale ? 0 : d;                          // (never beyond the committed row)
   int cnt = 0;
   for (int v0 = 0; v0 < total; v0 += 16) {
     const int v = v0 + l;
@@ -921,58 +889,43 @@ __global__ __launch_bounds__(256) void k_radius_rows_direct(int64_t n, const dou
       const double d2 = dist2<DIM>(q, sorted_pos + (int64_t)ps * DIM);
       hit = idx != (int)i && d2 <= r2;
     }
-    const unsigned m = (unsigned)((__ballot(hit) >> team_shift) & 0xffffu);
-    if (hit) {
-      const int at = cnt + __popc(m & ((1u << l) - 1u));
-      if (at < d) { if (in_lds) stg[at] = idx; else tmp[beg + at] = idx; }     // (never beyond the committed row)
-    }
-    cnt += __popc(m);
+    cnt += stage_hits(hit, idx, l, cnt, cap, in_lds, stg, tmp + beg);
   }
-  if (cnt != d) {                                         // the points changed under the captured graph: this row keeps its contents
-    if (l == 0) atomicOr(status, RGNN_STATUS_EDGE_COUNT_CHANGED);
+  if (stale || cnt != d) {                                // the points changed under the captured graph: the launch / this row writes nothing
+    if (l == 0 && (!stale || i == 0)) atomicOr(status, RGNN_STATUS_EDGE_COUNT_CHANGED);
     return;
   }
   if (d == 0) return;
-  auto emit = [&](int v, int rank) {
-    const int64_t pos = (int64_t)beg + rank;
-    col[pos] = v;
-    if (edge_index) {
-      edge_index[pos] = i;                               // E[:,0] = query point (graph.py:61)
-      edge_index[n_edges + pos] = v;                     // E[:,1] = neighbour   (graph.py:62)
-    }
-    if (rel_pos) {
-      double dx = q[0] - X[(int64_t)v * DIM], dy = q[1] - X[(int64_t)v * DIM + 1];      // graph.py:199-200
-      if (rel_undirected) { dx = fabs(dx); dy = fabs(dy); }
-      *(float2*)(rel_pos + pos * 2) = make_float2((float)dx, (float)dy);
-    }
-  };
-  if (in_lds) {
-    // (the team's lanes are lanes of one wave: its LDS writes are ordered before the reads below by the wave's own program order
-    //  plus an LDS wait)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_s_waitcnt(0xc07f);                   // lgkmcnt(0)
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    for (int c = l; c < d; c += 16) {
-      const int v = ((volatile int32_t*)stg)[c];
-      int rank = 0;
-      for (int o = 0; o < d; o++) rank += (((volatile int32_t*)stg)[o] < v) ? 1 : 0;
-      emit(v, rank);
-    }
-    return;
-  }
-  __threadfence();                                        // the staged row is read back by the other lanes of the team (L2)
-  for (int c = l; c < d; c += 16) {
-    const int v = __hip_atomic_load(tmp + beg + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int rank = 0;
-    for (int o = 0; o < d; o++) rank += (__hip_atomic_load(tmp + beg + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v) ? 1 : 0;
-    emit(v, rank);
-  }
+  const EdgeWriter out{col, edge_index, n_edges, rel_pos, rel_undirected};
+  rank_staged_row(in_lds, stg, tmp + beg, d, l,
+                  [&](int v, int rank) { out.edge((int64_t)beg + rank, (int)i, v, q[0], q[1], X + (int64_t)v * DIM); });
 }
 
 // ------------------------------------------------------------------------------------------------
 // kNN: ring expansion over the grid, k best candidates per thread kept in LDS
 // ------------------------------------------------------------------------------------------------
 constexpr int KNN_THREADS = 128;
+
+// The row of a query i whose frame has no more than k points (sklearn: "Expected n_neighbors < n_samples_fit"): k neighbours -1 and
+// the status bit.  The row's entries are dealt to the `team` lanes that share the query.
+__device__ __forceinline__ void knn_short_row(const EdgeWriter& out, int i, int k, int lane, int team, int32_t* status) {
+  if (lane == 0) atomicOr(status, RGNN_STATUS_KNN_TOO_FEW_POINTS);
+  for (int a = lane; a < k; a += team) out.ids((int64_t)i * k + a, i, -1);
+}
+
+// Ring termination of the grid walkers: every point not yet visited lies outside the block of cells [x0, x1] x [y0, y1] around the
+// query (qx, qy), so its distance is at least the query's distance to the nearest side of that block that is not the frame's own
+// edge.  -> that lower bound squared, or 0 when there is none (no distance is below it): the walk ends once the k-th best
+// distance is below it.
+__device__ __forceinline__ double knn_ring_bound(const FrameGrid& g, double qx, double qy, int x0, int x1, int y0, int y1) {
+  double lb = INFINITY;
+  if (x0 > 0) lb = fmin(lb, qx - (g.x0 + (double)x0 * g.h));
+  if (x1 < g.gx - 1) lb = fmin(lb, (g.x0 + (double)(x1 + 1) * g.h) - qx);
+  if (y0 > 0) lb = fmin(lb, qy - (g.y0 + (double)y0 * g.h));
+  if (y1 < g.gy - 1) lb = fmin(lb, (g.y0 + (double)(y1 + 1) * g.h) - qy);
+  lb -= 1e-9 * g.h;  // slack for the rounding of the binning division
+  return lb > 0 ? lb * lb : 0.0;
+}
 
 template <int DIM>
 __global__ __launch_bounds__(KNN_THREADS) void k_knn(int64_t n, int k, const FrameGrid* __restrict__ frames,
@@ -990,15 +943,8 @@ __global__ __launch_bounds__(KNN_THREADS) void k_knn(int64_t n, int k, const Fra
   if (p >= n) return;
   const FrameGrid g = frames[sorted_frame[p]];
   const int i = sorted_idx[p];
-  const int64_t E = n * (int64_t)k;
-  if (g.n_pts <= k) {  // sklearn: "Expected n_neighbors < n_samples_fit"
-    atomicOr(status, RGNN_STATUS_KNN_TOO_FEW_POINTS);
-    for (int a = 0; a < k; a++) {
-      nbr[(int64_t)i * k + a] = -1;
-      if (edge_index) { edge_index[(int64_t)i * k + a] = i; edge_index[E + (int64_t)i * k + a] = -1; }
-    }
-    return;
-  }
+  const EdgeWriter out{nbr, edge_index, n * (int64_t)k, nullptr, 0};
+  if (g.n_pts <= k) { knn_short_row(out, i, k, 0, 1, status); return; }
   int cx, cy;
   cell_xy(g, sorted_cell[p], cx, cy);
   double q[DIM];
@@ -1050,16 +996,7 @@ __global__ __launch_bounds__(KNN_THREADS) void k_knn(int64_t n, int k, const Fra
       }
     }
     if (x0 <= 0 && y0 <= 0 && x1 >= g.gx - 1 && y1 >= g.gy - 1) break;  // whole frame visited
-    if (count == k) {
-      // every unvisited point lies outside the visited block of cells: lower bound of its distance
-      double lb = INFINITY;
-      if (x0 > 0) lb = fmin(lb, q[0] - (g.x0 + (double)x0 * g.h));
-      if (x1 < g.gx - 1) lb = fmin(lb, (g.x0 + (double)(x1 + 1) * g.h) - q[0]);
-      if (y0 > 0) lb = fmin(lb, q[1] - (g.y0 + (double)y0 * g.h));
-      if (y1 < g.gy - 1) lb = fmin(lb, (g.y0 + (double)(y1 + 1) * g.h) - q[1]);
-      lb -= 1e-9 * g.h;  // slack for the rounding of the binning division
-      if (lb > 0 && worst_d < lb * lb) break;
-    }
+    if (count == k && worst_d < knn_ring_bound(g, q[0], q[1], x0, x1, y0, y1)) break;
   }
   // ascending (distance, index): selection sort in LDS, k is small
   for (int a = 0; a < k; a++) {
@@ -1077,9 +1014,7 @@ __global__ __launch_bounds__(KNN_THREADS) void k_knn(int64_t n, int k, const Fra
       sd[a * KNN_THREADS + t] = bd;
       si[a * KNN_THREADS + t] = bi;
     }
-    const int64_t e = (int64_t)i * k + a;
-    nbr[e] = bi;
-    if (edge_index) { edge_index[e] = i; edge_index[E + e] = bi; }
+    out.ids((int64_t)i * k + a, i, bi);
   }
 }
 
@@ -1113,15 +1048,8 @@ __global__ __launch_bounds__(256) void k_knn_team(int64_t n, int k, const FrameG
   if (p >= n) return;
   const FrameGrid g = frames[sorted_frame[p]];
   const int i = sorted_idx[p];
-  const int64_t E = n * (int64_t)k;
-  if (g.n_pts <= k) {  // sklearn: "Expected n_neighbors < n_samples_fit"
-    if (lane == 0) atomicOr(status, RGNN_STATUS_KNN_TOO_FEW_POINTS);
-    for (int a = lane; a < k; a += TEAM) {
-      nbr[(int64_t)i * k + a] = -1;
-      if (edge_index) { edge_index[(int64_t)i * k + a] = i; edge_index[E + (int64_t)i * k + a] = -1; }
-    }
-    return;
-  }
+  const EdgeWriter out{nbr, edge_index, n * (int64_t)k, rel_pos, rel_undirected};
+  if (g.n_pts <= k) { knn_short_row(out, i, k, lane, TEAM, status); return; }
   int cx, cy;
   cell_xy(g, sorted_cell[p], cx, cy);
   double q[DIM];
@@ -1261,30 +1189,15 @@ __global__ __launch_bounds__(256) void k_knn_team(int64_t n, int k, const FrameG
     }
     if (cnt >= k && dirty) prune();
     if (x0 <= 0 && y0 <= 0 && x1 >= g.gx - 1 && y1 >= g.gy - 1) break;  // whole frame visited
-    if (cnt == k) {
-      // every unvisited point lies outside the visited block of cells: lower bound of its distance
-      double lb = INFINITY;
-      if (x0 > 0) lb = fmin(lb, q[0] - (g.x0 + (double)x0 * g.h));
-      if (x1 < g.gx - 1) lb = fmin(lb, (g.x0 + (double)(x1 + 1) * g.h) - q[0]);
-      if (y0 > 0) lb = fmin(lb, q[1] - (g.y0 + (double)y0 * g.h));
-      if (y1 < g.gy - 1) lb = fmin(lb, (g.y0 + (double)(y1 + 1) * g.h) - q[1]);
-      lb -= 1e-9 * g.h;  // slack for the rounding of the binning division
-      if (lb > 0 && thr_d < lb * lb) break;
-    }
+    if (cnt == k && thr_d < knn_ring_bound(g, q[0], q[1], x0, x1, y0, y1)) break;
   }
   // the last prune left the k best in ascending (distance, index) order
   const KnnKey* S = buf[team][sel];
   if (degree_init && lane == 0) degree_init[i] = k;        // out-degree: what rgnn_undirected_degree_preset starts from
+  // (q is the cell-ordered copy of row i of X: the same float64 values)
   for (int a = lane; a < k; a += TEAM) {
     const int bi = S[a].i;
-    const int64_t e = (int64_t)i * k + a;
-    nbr[e] = bi;
-    if (edge_index) { edge_index[e] = i; edge_index[E + e] = bi; }
-    if (rel_pos) {                                         // relative_position of edge (i -> bi): graph.py:199-200
-      double dx = X[(int64_t)i * DIM] - X[(int64_t)bi * DIM], dy = X[(int64_t)i * DIM + 1] - X[(int64_t)bi * DIM + 1];
-      if (rel_undirected) { dx = fabs(dx); dy = fabs(dy); }
-      *(float2*)(rel_pos + e * 2) = make_float2((float)dx, (float)dy);
-    }
+    out.edge((int64_t)i * k + a, i, bi, q[0], q[1], X + (int64_t)bi * DIM);
   }
 }
 
@@ -1325,16 +1238,9 @@ __global__ __launch_bounds__(256) void k_knn_frame(int64_t n, int k, int n_frame
   const int nf = (int)(frame_ptr[f + 1] - beg);
   const int qs = (int)(w % waves_per_frame) * KF_QPW, qe = min(nf, qs + KF_QPW);
   if (qs >= nf) return;
-  const int64_t E = n * (int64_t)k;
-  if (nf <= k) {  // sklearn: "Expected n_neighbors < n_samples_fit"
-    if (lane == 0) atomicOr(status, RGNN_STATUS_KNN_TOO_FEW_POINTS);
-    for (int q = qs; q < qe; q++) {
-      const int i = sorted_idx[beg + q];
-      for (int a = lane; a < k; a += 64) {
-        nbr[(int64_t)i * k + a] = -1;
-        if (edge_index) { edge_index[(int64_t)i * k + a] = i; edge_index[E + (int64_t)i * k + a] = -1; }
-      }
-    }
+  const EdgeWriter out{nbr, edge_index, n * (int64_t)k, rel_pos, rel_undirected};
+  if (nf <= k) {
+    for (int q = qs; q < qe; q++) knn_short_row(out, sorted_idx[beg + q], k, lane, 64, status);
     return;
   }
   // this lane's candidates: points lane, lane + 64, ... of the frame (cell order)
@@ -1462,16 +1368,12 @@ __global__ __launch_bounds__(256) void k_knn_frame(int64_t n, int k, int n_frame
         rank += (db < da || (db == da && ib < ia)) ? 1 : 0;
       }
     }
+    // (the cell-ordered copies ARE the rows of X: same float64 values, so the same differences as from X[i] - X[ia])
+    // (ids and attr apart, so that the LDS reads stay under the test: k_knn_frame<2, 16> sits at 256 VGPRs and spills one more otherwise)
     if (lane < k) {
       const int64_t e = (int64_t)i * k + rank;
-      nbr[e] = ia;
-      if (edge_index) { edge_index[e] = i; edge_index[E + e] = ia; }
-      if (rel_pos) {                                         // relative_position of edge (i -> ia): graph.py:199-200
-        // (the cell-ordered copies ARE the rows of X: same float64 values, so the same differences as k_knn_team's X[i] - X[ia])
-        double dx = qp[0] - lx[lane], dy = qp[1] - ly[lane];
-        if (rel_undirected) { dx = fabs(dx); dy = fabs(dy); }
-        *(float2*)(rel_pos + e * 2) = make_float2((float)dx, (float)dy);
-      }
+      out.ids(e, i, ia);
+      if (rel_pos) out.attr(e, qp[0], qp[1], lx[lane], ly[lane]);
     }
     if (degree_init && lane == 0) degree_init[i] = k;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -1743,6 +1645,15 @@ __global__ __launch_bounds__(256) void k_sym_csr(const int64_t* __restrict__ edg
 }  // namespace
 
 // ================================================================================================
+// The one dimension dispatch: runs the statement(s) with the grid's dim (2, 4 or 8: check_grid) as the constant DIM, for use as a
+// template argument.
+#define RGNN_WITH_DIM(dim, ...)                                          \
+  do {                                                                   \
+    if ((dim) == 2) { constexpr int DIM = 2; __VA_ARGS__; }              \
+    else if ((dim) == 4) { constexpr int DIM = 4; __VA_ARGS__; }         \
+    else { constexpr int DIM = 8; __VA_ARGS__; }                         \
+  } while (0)
+
 extern "C" int64_t rgnn_grid_workspace_bytes(int64_t n, int64_t n_frames, int32_t dim) {
   if (n < 0 || n_frames < 0 || (dim != 2 && dim != 4 && dim != 8)) return -1;
   return make_view(nullptr, n, n_frames, dim).total_bytes;
@@ -1790,18 +1701,11 @@ extern "C" int rgnn_grid_build(const rgnn_grid* g, double cell_size, double pts_
       hipLaunchKernelGGL(k_grid_frame_reg, dim3((unsigned)g->n_frames), dim3(GF_THREADS), (2 * (size_t)lds_cells + GFR_PPT * GF_THREADS) * 4, s,
                          g->X, g->frame_ptr, (int)g->n_frames, v.frames, cell_size, pts_per_cell, v.cell_count, v.cell_start, v.n_cells,
                          lds_cells, v.sorted_idx, v.sorted_frame, v.sorted_cell, v.sorted_pos, v.point_cell, v.point_frame, v.point_rank);
-    } else if (g->dim == 2)
-      hipLaunchKernelGGL(k_grid_frame<2>, dim3((unsigned)g->n_frames), dim3(GF_THREADS), (size_t)lds_cells * 4, s, g->X, g->frame_ptr,
-                         (int)g->n_frames, v.frames, cell_size, pts_per_cell, v.cell_count, v.cell_start, v.n_cells, lds_cells,
-                         v.sorted_idx, v.sorted_frame, v.sorted_cell, v.sorted_pos, v.point_cell, v.point_frame, v.point_rank);
-    else if (g->dim == 4)
-      hipLaunchKernelGGL(k_grid_frame<4>, dim3((unsigned)g->n_frames), dim3(GF_THREADS), (size_t)lds_cells * 4, s, g->X, g->frame_ptr,
-                         (int)g->n_frames, v.frames, cell_size, pts_per_cell, v.cell_count, v.cell_start, v.n_cells, lds_cells,
-                         v.sorted_idx, v.sorted_frame, v.sorted_cell, v.sorted_pos, v.point_cell, v.point_frame, v.point_rank);
-    else
-      hipLaunchKernelGGL(k_grid_frame<8>, dim3((unsigned)g->n_frames), dim3(GF_THREADS), (size_t)lds_cells * 4, s, g->X, g->frame_ptr,
-                         (int)g->n_frames, v.frames, cell_size, pts_per_cell, v.cell_count, v.cell_start, v.n_cells, lds_cells,
-                         v.sorted_idx, v.sorted_frame, v.sorted_cell, v.sorted_pos, v.point_cell, v.point_frame, v.point_rank);
+    } else
+      RGNN_WITH_DIM(g->dim, hipLaunchKernelGGL(k_grid_frame<DIM>, dim3((unsigned)g->n_frames), dim3(GF_THREADS), (size_t)lds_cells * 4, s, g->X,
+                                               g->frame_ptr, (int)g->n_frames, v.frames, cell_size, pts_per_cell, v.cell_count, v.cell_start,
+                                               v.n_cells, lds_cells, v.sorted_idx, v.sorted_frame, v.sorted_cell, v.sorted_pos, v.point_cell,
+                                               v.point_frame, v.point_rank));
     RGNN_CHECK_LAUNCH();
     return RGNN_OK;
   }
@@ -1813,15 +1717,8 @@ extern "C" int rgnn_grid_build(const rgnn_grid* g, double cell_size, double pts_
   if (rc) return rc;
   hipLaunchKernelGGL(k_bin_scatter, dim3(rgnn_blocks(g->n, 256)), dim3(256), 0, s, g->n, v.point_cell, v.cell_start, v.cell_count, v.sorted_cell,
                      v.point_rank);
-  if (g->dim == 2)
-    hipLaunchKernelGGL(k_bin_place<2>, dim3(rgnn_blocks(g->n, 256)), dim3(256), 0, s, g->X, g->n, v.point_cell, v.point_frame, v.cell_start,
-                       (const int32_t*)v.sorted_cell, v.sorted_idx, v.sorted_frame, v.sorted_pos, v.point_rank);
-  else if (g->dim == 4)
-    hipLaunchKernelGGL(k_bin_place<4>, dim3(rgnn_blocks(g->n, 256)), dim3(256), 0, s, g->X, g->n, v.point_cell, v.point_frame, v.cell_start,
-                       (const int32_t*)v.sorted_cell, v.sorted_idx, v.sorted_frame, v.sorted_pos, v.point_rank);
-  else
-    hipLaunchKernelGGL(k_bin_place<8>, dim3(rgnn_blocks(g->n, 256)), dim3(256), 0, s, g->X, g->n, v.point_cell, v.point_frame, v.cell_start,
-                       (const int32_t*)v.sorted_cell, v.sorted_idx, v.sorted_frame, v.sorted_pos, v.point_rank);
+  RGNN_WITH_DIM(g->dim, hipLaunchKernelGGL(k_bin_place<DIM>, dim3(rgnn_blocks(g->n, 256)), dim3(256), 0, s, g->X, g->n, v.point_cell, v.point_frame,
+                                           v.cell_start, (const int32_t*)v.sorted_cell, v.sorted_idx, v.sorted_frame, v.sorted_pos, v.point_rank));
   hipLaunchKernelGGL(k_bin_cells, dim3(rgnn_blocks(g->n, 256)), dim3(256), 0, s, g->n, v.point_cell, v.point_rank, v.sorted_cell);
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
@@ -1839,18 +1736,9 @@ static int launch_radius(const rgnn_grid* g, double r, int32_t* deg, const int32
   hipStream_t s = (hipStream_t)stream;
   int32_t* unsorted = FILL ? tmp : nullptr;
   int32_t* row_tmp = FILL ? tmp + n_edges : nullptr;
-  if (g->dim == 2)
-    hipLaunchKernelGGL((k_radius<2, FILL>), dim3(rgnn_blocks(g->n, 256)), dim3(256), 0, s, g->n, g->X, v.point_cell,
-                       v.point_frame, v.frames, v.cell_start, v.sorted_idx, v.sorted_frame, v.sorted_cell, v.sorted_pos, r2,
-                       deg, rowptr, unsorted, row_tmp, v.nbr_cache, n_edges, status);
-  else if (g->dim == 4)
-    hipLaunchKernelGGL((k_radius<4, FILL>), dim3(rgnn_blocks(g->n, 256)), dim3(256), 0, s, g->n, g->X, v.point_cell,
-                       v.point_frame, v.frames, v.cell_start, v.sorted_idx, v.sorted_frame, v.sorted_cell, v.sorted_pos, r2,
-                       deg, rowptr, unsorted, row_tmp, v.nbr_cache, n_edges, status);
-  else
-    hipLaunchKernelGGL((k_radius<8, FILL>), dim3(rgnn_blocks(g->n, 256)), dim3(256), 0, s, g->n, g->X, v.point_cell,
-                       v.point_frame, v.frames, v.cell_start, v.sorted_idx, v.sorted_frame, v.sorted_cell, v.sorted_pos, r2,
-                       deg, rowptr, unsorted, row_tmp, v.nbr_cache, n_edges, status);
+  RGNN_WITH_DIM(g->dim, hipLaunchKernelGGL((k_radius<DIM, FILL>), dim3(rgnn_blocks(g->n, 256)), dim3(256), 0, s, g->n, g->X, v.point_cell,
+                                           v.point_frame, v.frames, v.cell_start, v.sorted_idx, v.sorted_frame, v.sorted_cell, v.sorted_pos,
+                                           r2, deg, rowptr, unsorted, row_tmp, v.nbr_cache, n_edges, status));
   if (FILL)
     hipLaunchKernelGGL(k_rank_rows, dim3(rgnn_blocks(n_edges, 256)), dim3(256), 0, s, rowptr, row_tmp, unsorted, n_edges,
                        col, edge_index, g->n, status != nullptr ? 1 : 0);
@@ -1898,18 +1786,9 @@ extern "C" int rgnn_radius_graph_rows(const rgnn_grid* g, double r, const int32_
   GridView v = make_view(g->ws, g->n, g->n_frames, g->dim);
   hipStream_t s = (hipStream_t)stream;
   const double r2 = r * r;
-  if (g->dim == 2)
-    hipLaunchKernelGGL(k_radius_rows<2>, dim3(rgnn_blocks(g->n, 16)), dim3(256), 0, s, g->n, g->X, v.point_cell, v.point_frame, v.frames,
-                       v.cell_start, v.sorted_idx, v.sorted_pos, r2, rowptr, v.nbr_cache, tmp, n_edges, status != nullptr ? 1 : 0, col,
-                       edge_index, relative_position, undirected, status);
-  else if (g->dim == 4)
-    hipLaunchKernelGGL(k_radius_rows<4>, dim3(rgnn_blocks(g->n, 16)), dim3(256), 0, s, g->n, g->X, v.point_cell, v.point_frame, v.frames,
-                       v.cell_start, v.sorted_idx, v.sorted_pos, r2, rowptr, v.nbr_cache, tmp, n_edges, status != nullptr ? 1 : 0, col,
-                       edge_index, relative_position, undirected, status);
-  else
-    hipLaunchKernelGGL(k_radius_rows<8>, dim3(rgnn_blocks(g->n, 16)), dim3(256), 0, s, g->n, g->X, v.point_cell, v.point_frame, v.frames,
-                       v.cell_start, v.sorted_idx, v.sorted_pos, r2, rowptr, v.nbr_cache, tmp, n_edges, status != nullptr ? 1 : 0, col,
-                       edge_index, relative_position, undirected, status);
+  RGNN_WITH_DIM(g->dim, hipLaunchKernelGGL(k_radius_rows<DIM>, dim3(rgnn_blocks(g->n, 16)), dim3(256), 0, s, g->n, g->X, v.point_cell, v.point_frame,
+                                           v.frames, v.cell_start, v.sorted_idx, v.sorted_pos, r2, rowptr, v.nbr_cache, tmp, n_edges,
+                                           status != nullptr ? 1 : 0, col, edge_index, relative_position, undirected, status));
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
 }
@@ -1925,12 +1804,9 @@ extern "C" int rgnn_radius_graph_rows_direct(const rgnn_grid* g, double r, const
   GridView v = make_view(g->ws, g->n, g->n_frames, g->dim);
   hipStream_t s = (hipStream_t)stream;
   const double r2 = r * r;
-#define RGNN_RD(D)                                                                                                                 \
-  hipLaunchKernelGGL(k_radius_rows_direct<D>, dim3(rgnn_blocks(g->n, 16)), dim3(256), 0, s, g->n, g->X, v.point_cell, v.point_frame,   \
-                     v.frames, v.cell_start, v.sorted_idx, v.sorted_pos, r2, rowptr_committed, tmp, n_edges, col, edge_index,      \
-                     relative_position, undirected, status)
-  if (g->dim == 2) RGNN_RD(2); else if (g->dim == 4) RGNN_RD(4); else RGNN_RD(8);
-#undef RGNN_RD
+  RGNN_WITH_DIM(g->dim, hipLaunchKernelGGL(k_radius_rows_direct<DIM>, dim3(rgnn_blocks(g->n, 16)), dim3(256), 0, s, g->n, g->X, v.point_cell,
+                                           v.point_frame, v.frames, v.cell_start, v.sorted_idx, v.sorted_pos, r2, rowptr_committed, tmp,
+                                           n_edges, col, edge_index, relative_position, undirected, status));
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
 }
@@ -2005,33 +1881,15 @@ static int knn_grid_walk(const rgnn_grid* g, int32_t k, int32_t* nbr, int64_t* e
   hipLaunchKernelGGL((k_knn_team<DIM, TEAM>), dim3(rgnn_blocks(g->n, 256 / TEAM)), dim3(256), 0, s, g->n, k, v.frames, \
                      v.cell_start, v.sorted_idx, v.sorted_frame, v.sorted_cell, v.sorted_pos, nbr, edge_index, status,      \
                      (const double*)g->X, relative_position, (int)undirected, degree_init)
-    if (g->dim == 2) {
-      if (team == 16) RGNN_KNN_TEAM_GO(2, 16); else if (team == 32) RGNN_KNN_TEAM_GO(2, 32); else RGNN_KNN_TEAM_GO(2, 64);
-    } else if (g->dim == 4) {
-      if (team == 16) RGNN_KNN_TEAM_GO(4, 16); else if (team == 32) RGNN_KNN_TEAM_GO(4, 32); else RGNN_KNN_TEAM_GO(4, 64);
-    } else {
-      if (team == 16) RGNN_KNN_TEAM_GO(8, 16); else if (team == 32) RGNN_KNN_TEAM_GO(8, 32); else RGNN_KNN_TEAM_GO(8, 64);
-    }
+    RGNN_WITH_DIM(g->dim, if (team == 16) RGNN_KNN_TEAM_GO(DIM, 16); else if (team == 32) RGNN_KNN_TEAM_GO(DIM, 32); else RGNN_KNN_TEAM_GO(DIM, 64));
 #undef RGNN_KNN_TEAM_GO
     RGNN_CHECK_LAUNCH();
     return RGNN_OK;
   }
-  if (g->dim == 2) {
-    if (lds > 64 * 1024)
-      hipFuncSetAttribute((const void*)k_knn<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k_knn<2>, dim3(rgnn_blocks(g->n, KNN_THREADS)), dim3(KNN_THREADS), lds, s, g->n, k, v.frames,
-                       v.cell_start, v.sorted_idx, v.sorted_frame, v.sorted_cell, v.sorted_pos, nbr, edge_index, status);
-  } else if (g->dim == 4) {
-    if (lds > 64 * 1024)
-      hipFuncSetAttribute((const void*)k_knn<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k_knn<4>, dim3(rgnn_blocks(g->n, KNN_THREADS)), dim3(KNN_THREADS), lds, s, g->n, k, v.frames,
-                       v.cell_start, v.sorted_idx, v.sorted_frame, v.sorted_cell, v.sorted_pos, nbr, edge_index, status);
-  } else {
-    if (lds > 64 * 1024)
-      hipFuncSetAttribute((const void*)k_knn<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k_knn<8>, dim3(rgnn_blocks(g->n, KNN_THREADS)), dim3(KNN_THREADS), lds, s, g->n, k, v.frames,
-                       v.cell_start, v.sorted_idx, v.sorted_frame, v.sorted_cell, v.sorted_pos, nbr, edge_index, status);
-  }
+  RGNN_WITH_DIM(g->dim,
+                if (lds > 64 * 1024) hipFuncSetAttribute((const void*)k_knn<DIM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                hipLaunchKernelGGL(k_knn<DIM>, dim3(rgnn_blocks(g->n, KNN_THREADS)), dim3(KNN_THREADS), lds, s, g->n, k, v.frames, v.cell_start,
+                                   v.sorted_idx, v.sorted_frame, v.sorted_cell, v.sorted_pos, nbr, edge_index, status));
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
 }

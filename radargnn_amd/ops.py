@@ -322,15 +322,23 @@ def radius_grid(X: torch.Tensor, frame_ptr: torch.Tensor, r: float, static: dict
     return g
 
 
+def _row_outputs(n_edges: int, device, want_edge_index: bool, relative_position: Optional[str], tmp_rows: int = 1):
+    """The buffers of a fill launch, sized for ``n_edges``: -> col int32 [E], edge_index int64 [2, E] or None, relative_position
+    float32 [E, 2] or None, the launch's int32 scratch [tmp_rows * E]."""
+    col = torch.empty(n_edges, dtype=torch.int32, device=device)
+    ei = torch.empty((2, n_edges), dtype=torch.int64, device=device) if want_edge_index else None
+    rel = torch.empty((n_edges, 2), dtype=torch.float32, device=device) if relative_position else None
+    tmp = torch.empty(max(tmp_rows * n_edges, 1), dtype=torch.int32, device=device)
+    return col, ei, rel, tmp
+
+
 def radius_graph_rows_direct(g: "GridHash", rowptr_committed: torch.Tensor, r: float, n_edges: int, status: torch.Tensor,
                              want_edge_index: bool = True, relative_position: Optional[str] = None):
     """Search + fill in one launch for a replayed step (rgnn_radius_graph_rows_direct): rows of the committed lengths are written at
-    the committed places, any other row keeps its contents and sets STATUS_EDGE_COUNT_CHANGED.  -> (col, edge_index[, rel])."""
+    the committed places, any other row keeps its contents and sets STATUS_EDGE_COUNT_CHANGED; so does ``rowptr_committed[-1] !=
+    n_edges`` (the size of the buffers), and the launch then writes nothing.  -> (col, edge_index[, rel])."""
     _dev(rowptr_committed, "rowptr_committed", torch.int32)
-    col = torch.empty(n_edges, dtype=torch.int32, device=rowptr_committed.device)
-    ei = torch.empty((2, n_edges), dtype=torch.int64, device=rowptr_committed.device) if want_edge_index else None
-    rel = torch.empty((n_edges, 2), dtype=torch.float32, device=rowptr_committed.device) if relative_position else None
-    tmp = torch.empty(max(n_edges, 1), dtype=torch.int32, device=rowptr_committed.device)
+    col, ei, rel, tmp = _row_outputs(n_edges, rowptr_committed.device, want_edge_index, relative_position)
     check(lib.rgnn_radius_graph_rows_direct(C.byref(g.desc), float(r), _ptr(rowptr_committed), _ptr(col), _ptr(ei), n_edges, _ptr(tmp),
                                             _ptr(status), _ptr(rel), 1 if relative_position == "undirected" else 0, _stream()))
     return (col, ei, rel) if relative_position else (col, ei)
@@ -346,15 +354,12 @@ def radius_graph_fill(g: "GridHash", rowptr: torch.Tensor, r: float, n_edges: in
     the device, write nothing otherwise and set STATUS_EDGE_COUNT_CHANGED in it.
     ``relative_position`` ("directed" | "undirected"): also return the relative_position edge attributes float32 [E, 2] as a
     third value -- written by the same launch (rgnn_radius_graph_rows)."""
-    col = torch.empty(n_edges, dtype=torch.int32, device=rowptr.device)
-    ei = torch.empty((2, n_edges), dtype=torch.int64, device=rowptr.device) if want_edge_index else None
     if FUSED_RADIUS_ROWS:
-        rel = torch.empty((n_edges, 2), dtype=torch.float32, device=rowptr.device) if relative_position else None
-        tmp = torch.empty(max(n_edges, 1), dtype=torch.int32, device=rowptr.device)
+        col, ei, rel, tmp = _row_outputs(n_edges, rowptr.device, want_edge_index, relative_position)
         check(lib.rgnn_radius_graph_rows(C.byref(g.desc), float(r), _ptr(rowptr), _ptr(col), _ptr(ei), n_edges, _ptr(tmp),
                                          _ptr(guard_status), _ptr(rel), 1 if relative_position == "undirected" else 0, _stream()))
         return (col, ei, rel) if relative_position else (col, ei)
-    tmp = torch.empty(max(2 * n_edges, 1), dtype=torch.int32, device=rowptr.device)
+    col, ei, _, tmp = _row_outputs(n_edges, rowptr.device, want_edge_index, None, tmp_rows=2)     # (unsorted rows + their row ids)
     check(lib.rgnn_radius_graph_fill(C.byref(g.desc), float(r), _ptr(rowptr), _ptr(col), _ptr(ei), n_edges, _ptr(tmp),
                                      _ptr(guard_status), _stream()))
     if relative_position:

@@ -145,7 +145,7 @@ def geometry_frames(r=GEOMETRY_R):
 
 
 def frame_grid(X, cell_size=0.0, pts_per_cell=2.0):
-    """k_frame_grid's arithmetic (csrc/graph.hip), step by step, in float64 -> dict(h, gx, gy, cells, cap, grows, branch)."""
+    """frame_grid_geometry's arithmetic (csrc/graph.hip: the one function every grid build calls), step by step, in float64 -> dict(h, gx, gy, cells, cap, grows, branch)."""
     n = X.shape[0]
     cap = CELLS_PER_POINT * n + CELLS_PER_FRAME
     ex = float(X[:, 0].max() - X[:, 0].min())

@@ -157,6 +157,46 @@ def test_radius_row_lengths_at_every_threshold(ops):
                 assert torch.equal(rel2, out["rel"])
 
 
+def test_rows_direct_writes_nothing_under_another_edge_total(ops):
+    """rgnn_radius_graph_rows_direct with committed rows whose total E is not the n_edges the buffers were sized for (E - 1 and
+    E + 1): STATUS_EDGE_COUNT_CHANGED, and not one element of col / edge_index / relative_position written -- what the guarded
+    k_radius_rows does.  The star batch: its hub rows of 129 and 513 neighbours take the LDS stage and the global scratch.  Then
+    n_edges = E on the same buffers: a clean status and ops.radius_graph_fill's outputs, so the guard refuses nothing it should
+    accept.  The C entry point is called directly, because the ops wrapper sizes the buffers from n_edges: here they hold
+    max(E, n_edges) edges, so no kernel, guarded or not, writes outside an allocation."""
+    import ctypes as C
+    from radargnn_amd import _lib
+    frames, _ = gi.star_batch()
+    r = gi.STAR_R
+    Xb, ptr = batch(frames)
+    X, P = dev(Xb), dev(ptr)
+    static = {}
+    g, rowptr = ops.radius_graph_count(X, P, r, static=static)
+    rows = rowptr.clone()
+    E = int(rows[-1].item())
+    assert E > 513
+    cap, sentinel = E + 1, -7
+    col = torch.full((cap,), sentinel, dtype=torch.int32, device=X.device)
+    ei = torch.full((2 * cap,), sentinel, dtype=torch.int64, device=X.device)
+    rel = torch.full((cap, 2), float(sentinel), dtype=torch.float32, device=X.device)
+    tmp = torch.full((cap,), sentinel, dtype=torch.int32, device=X.device)
+    status = torch.zeros(1, dtype=torch.int32, device=X.device)
+
+    def run(n_edges):
+        status.zero_()
+        _lib.check(_lib.lib.rgnn_radius_graph_rows_direct(C.byref(g.desc), float(r), ops._ptr(rows), ops._ptr(col), ops._ptr(ei), n_edges,
+                                                          ops._ptr(tmp), ops._ptr(status), ops._ptr(rel), 0, ops._stream()))
+        torch.cuda.synchronize()
+        return int(status.item())
+
+    for n_edges in (E - 1, E + 1):
+        assert run(n_edges) & ops.STATUS_EDGE_COUNT_CHANGED, n_edges
+        assert bool((col == sentinel).all()) and bool((ei == sentinel).all()) and bool((rel == float(sentinel)).all()), n_edges
+    assert run(E) == 0
+    col0, ei0, rel0 = ops.radius_graph_fill(g, rows, r, E, relative_position="directed")
+    assert torch.equal(col[:E], col0) and torch.equal(ei[:2 * E].view(2, E), ei0) and torch.equal(rel[:E], rel0)
+
+
 def geometry_batch():
     fr = gi.geometry_frames()
     order = ["clusters", "single", "line_h", "empty", "line_v", "coincident", "pair_at_r", "pair_beyond_r", "negative"]

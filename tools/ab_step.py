@@ -1,6 +1,9 @@
 """Step times of the BASELINE configurations with whatever build of librgnn RGNN_LIB names (default: the in-tree one): for A/B runs of
 kernel variants on ONE box in ONE gpurun call (the pool's boxes differ by several per cent).
-    python tools/ab_step.py [--cases c2,c3,c4,c5] [--steps 30]"""
+    python tools/ab_step.py [--cases c2,c3,c4,c5] [--steps 30] [--digest]
+--digest: instead of times, a SHA-256 per case over the graph stage's outputs (x, edge_index, edge_attr, degree, cell_order, rowptr
+where present) and the model's two outputs after the warm-up passes -- equal digests from two builds: identical bits."""
+import hashlib
 import os
 import sys
 import time
@@ -25,14 +28,28 @@ def timed(hot, batches, steps):
     return (time.perf_counter() - t0) / steps / len(batches) * 1e3
 
 
+def digest(hot, batches):
+    for _ in range(4):
+        for b in batches:
+            out = hot(b)
+    torch.cuda.synchronize()
+    cls, bb, g = out
+    h = hashlib.sha256()
+    for t in (g.x, g.edge_index, g.edge_attr, g.degree, g.cell_order, g.rowptr, cls, bb):
+        if t is not None:
+            h.update(t.detach().contiguous().cpu().numpy().tobytes())
+    return h.hexdigest()
+
+
 def main():
     argv = sys.argv[1:]
-    cases, steps, kernels = ["c2", "c3", "c4"], 30, False
+    cases, steps, kernels, digests = ["c2", "c3", "c4"], 30, False, False
     while argv:
         a = argv.pop(0)
         if a == "--cases": cases = argv.pop(0).split(",")
         elif a == "--steps": steps = int(argv.pop(0))
         elif a == "--kernels": kernels = True
+        elif a == "--digest": digests = True
     out = {}
     rs = lambda a, b: [synthetic.radarscenes_frame(i) for i in range(a, b)]
     for c in cases:
@@ -49,6 +66,9 @@ def main():
                                    edge_features=("point_pair_features",))
             fb, graph = [[synthetic.stress_cloud()]], True
         batches = [fr.FrameBatch.from_frames(f) for f in fb]
+        if digests:
+            out[c] = digest(fr.HotPath(model, cfg, use_hip_graphs=graph), batches)
+            continue
         out[c] = round(timed(fr.HotPath(model, cfg, use_hip_graphs=graph), batches, steps), 4)
         if kernels:                                     # HIP events inside librgnn around the edge / dense launches (eager pass)
             summ = bench.instrumented(model, cfg, batches[:1], 5, c in ("c2", "c5"))
