@@ -170,6 +170,24 @@ int rgnn_radius_rows_commit(const int32_t* rowptr_new /*[dev] n+1*/, int64_t n, 
                             lengths travel with the rows (degree feature, lists of nodes with / without edges)*/,
                             rgnn_stream_t stream);
 
+/* Radius graph with a neighbour cap, 1 <= k <= 128 (anything else: RGNN_ERR_INVALID_ARGUMENT): with S_i the row of the radius graph
+ * (j != i, same frame, d2 <= r*r), row i is S_i when |S_i| <= k and otherwise the k entries of S_i smallest under the key (d2, j) --
+ * distance ascending, a tie at the cut to the smaller index: the order of rgnn_knn_graph.  Rows are stored with ascending neighbour
+ * ids, like rgnn_radius_graph_rows.  The graph is a function of the points alone (no atomics decide anything) and, unlike the radius
+ * graph, NOT symmetric.  No reference counterpart (PyG's radius_graph(max_num_neighbors) truncates arbitrarily).
+ * Protocol (same grid, same r and k in both calls):
+ *   rgnn_radius_graph_capped_count   full[i] = |S_i| (int32 [n]) and lens (int32 [2 n]): lens[i] = min(|S_i|, k), lens[n + i] = the
+ *                                    row's scratch entries in pass 2 (|S_i| for rows of more than 128 candidates, else 0);
+ *   rgnn_exclusive_scan_i32          ptr (int32 [2 n + 1]) = scan of lens: ptr[0 .. n] is the rowptr, E = ptr[n], and the scratch
+ *                                    holds n_spill = ptr[2 n] - ptr[n] entries -- both totals in one host read;
+ *   rgnn_radius_graph_capped_rows    col int32 [E], edge_index int64 [2, E] or NULL.  spill: [dev] 12 * n_spill bytes, 8-byte
+ *                                    aligned (NULL when n_spill == 0). */
+int rgnn_radius_graph_capped_count(const rgnn_grid* g, double r, int32_t k, int32_t* full /*[dev] n*/, int32_t* lens /*[dev] 2 n*/,
+                                   rgnn_stream_t stream);
+int rgnn_radius_graph_capped_rows(const rgnn_grid* g, double r, int32_t k, const int32_t* full /*[dev] n*/,
+                                  const int32_t* ptr /*[dev] 2 n + 1*/, int32_t* col /*[dev]*/, int64_t* edge_index /*[dev] or NULL*/,
+                                  int64_t n_edges, void* spill /*[dev] or NULL*/, int64_t n_spill, rgnn_stream_t stream);
+
 /* k nearest neighbours excluding self; nbr int32 [n,k], each row ordered (distance asc, index asc).  Optionally writes edge_index
  * int64 [2, n*k].  status gets RGNN_STATUS_KNN_TOO_FEW_POINTS if a frame has <= k points (rows of that frame are filled with -1).
  * Replaces sklearn kneighbors_graph behind graph_constructor/graph.py:52-66.  The write-out can do more (the team kernel has the

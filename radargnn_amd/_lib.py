@@ -60,6 +60,8 @@ SIGNATURES = {
     "rgnn_radius_graph_rows": (c_i32, [C.POINTER(RgnnGrid), c_f64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "rgnn_radius_graph_rows_direct": (c_i32, [C.POINTER(RgnnGrid), c_f64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "rgnn_radius_rows_commit": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_radius_graph_capped_count": (c_i32, [C.POINTER(RgnnGrid), c_f64, c_i32, c_vp, c_vp, c_vp]),
+    "rgnn_radius_graph_capped_rows": (c_i32, [C.POINTER(RgnnGrid), c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "rgnn_knn_graph": (c_i32, [C.POINTER(RgnnGrid), c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "rgnn_knn_degree_from_csr": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "rgnn_undirected_degree_preset": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),

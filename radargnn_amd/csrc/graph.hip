@@ -1822,6 +1822,263 @@ extern "C" int rgnn_radius_rows_commit(const int32_t* rowptr_new, int64_t n, int
   return RGNN_OK;
 }
 
+namespace {
+// ------------------------------------------------------------------------------------------------
+// radius graph with a neighbour cap: the k nearest of the points within r
+//
+// S_i = the row the radius search finds (j != i, same frame, d2 <= r2), m = |S_i|.  A row of m <= k entries is S_i; a longer one keeps
+// the k entries smallest under the key (d2, j) -- the order of the kNN kernels: distance asc, index asc -- and is stored, like every
+// radius row, with ascending neighbour ids.  The count pass is the radius graph's own (k_radius<., false>: m per point and the first
+// RADIUS_CACHE neighbours in the cache); k_capped_lengths turns m into the two lengths the fill needs, ONE scan over both gives the
+// rows and the scratch slices, and k_radius_capped_rows writes the rows, a team of 16 lanes per point like k_radius_rows:
+//   m <= RADIUS_CACHE   the candidates come from the cache; a row that is cut gets its distances from X (dist2 on the same float64
+//                       values in the same order as the search: the same bits) and is selected and ranked with shuffles;
+//   m <= k              (beyond the cache) searched again, ids staged in LDS and ranked: exactly what k_radius_rows does;
+//   m > k               searched again, (d2, j) staged -- in LDS up to CAPPED_LDS candidates, beyond that in the row's slice of the
+//                       global scratch --, an entry is kept iff fewer than k staged entries have a smaller key (keys are unique:
+//                       exactly k are kept), the kept ids are compacted into LDS and ranked.
+// Every decision is a count over the row's own entries: no atomics, nothing depends on the order the candidates arrive in.
+// ------------------------------------------------------------------------------------------------
+constexpr int CAPPED_LDS = KNN_CAP;                   // candidates of a cut row staged in LDS (12 B each); k <= KNN_CAP <= CAPPED_LDS
+
+// lens[i] = min(m, k): the row's length; lens[n + i] = m where the row's candidates go to the global scratch, else 0.
+__global__ __launch_bounds__(256) void k_capped_lengths(const int32_t* __restrict__ full, int64_t n, int k, int32_t* __restrict__ lens) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int m = full[i];
+  lens[i] = min(m, k);
+  lens[n + i] = m > CAPPED_LDS ? m : 0;
+}
+
+__device__ __forceinline__ double shfl16(double v, int src) {
+  int2 t = __builtin_bit_cast(int2, v);
+  t.x = __shfl(t.x, src, 16); t.y = __shfl(t.y, src, 16);
+  return __builtin_bit_cast(double, t);
+}
+__device__ __forceinline__ bool key_less(double da, int ja, double db, int jb) { return da < db || (da == db && ja < jb); }
+
+// The staged candidates (d2, j) of a cut row, in LDS or in the row's slice of the global scratch; written by the lanes that found
+// them, read back by all lanes of the team (same wave: see rank_staged_row for the ordering of either memory).
+template <bool LDS>
+struct StagedKeys {
+  double* d;
+  int32_t* j;
+  __device__ __forceinline__ void put(int at, double d2, int idx) const { d[at] = d2; j[at] = idx; }
+  __device__ __forceinline__ void publish() const {
+    if (LDS) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_s_waitcnt(0xc07f);                 // lgkmcnt(0)
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else {
+      __threadfence();
+    }
+  }
+  __device__ __forceinline__ double dist(int o) const {
+    if (LDS) return ((const volatile double*)d)[o];
+    return __longlong_as_double((long long)__hip_atomic_load((const unsigned long long*)d + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  }
+  __device__ __forceinline__ int id(int o) const {
+    if (LDS) return ((const volatile int32_t*)j)[o];
+    return __hip_atomic_load(j + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
+
+// The 3 x 3 cells around query i, 16 candidates a trip (lane l takes candidate l of the trip): found(hit, idx, d2) once per trip,
+// by all lanes of the team.
+template <int DIM, class Found>
+__device__ __forceinline__ void walk_cells_team(const double* q, int i, const FrameGrid& g, int cell, const int32_t* __restrict__ cell_start,
+                                                const int32_t* __restrict__ sorted_idx, const double* __restrict__ sorted_pos, double r2,
+                                                int l, Found found) {
+  int cx, cy;
+  cell_xy(g, cell, cx, cy);
+  for (int u = 0; u < 9; u++) {
+    const int xx = cx + (u % 3) - 1, yy = cy + (u / 3) - 1;
+    if (xx < 0 || xx >= g.gx || yy < 0 || yy >= g.gy) continue;
+    const int c = cell_id(g, xx, yy);
+    const int b = cell_start[c], en = cell_start[c + 1];
+    for (int pp = b; pp < en; pp += 16) {
+      const int ps = pp + l;
+      bool hit = false;
+      int idx = 0;
+      double d2 = 0.0;
+      if (ps < en) {
+        idx = sorted_idx[ps];
+        d2 = dist2<DIM>(q, sorted_pos + (int64_t)ps * DIM);
+        hit = idx != i && d2 <= r2;
+      }
+      found(hit, idx, d2);
+    }
+  }
+}
+
+// A cut row beyond the cache: search, stage (d2, j), keep the k smallest keys, compact the kept ids into `kept` (LDS, KNN_CAP
+// entries) -> their number (k, and never more than `d` = the row's length).
+template <int DIM, bool LDS>
+__device__ __forceinline__ int select_staged_row(const double* q, int i, const FrameGrid& g, int cell, const int32_t* __restrict__ cell_start,
+                                                 const int32_t* __restrict__ sorted_idx, const double* __restrict__ sorted_pos, double r2,
+                                                 int l, int m, int k, int d, StagedKeys<LDS> st, int32_t* kept) {
+  const int team_shift = (threadIdx.x & 63) & ~15;       // this team's bits in a wave-wide ballot
+  const unsigned below_l = (1u << l) - 1u;
+  int cnt = 0;
+  walk_cells_team<DIM>(q, i, g, cell, cell_start, sorted_idx, sorted_pos, r2, l, [&](bool hit, int idx, double d2) {
+    const unsigned mk = (unsigned)((__ballot(hit) >> team_shift) & 0xffffu);
+    if (hit) {
+      const int at = cnt + __popc(mk & below_l);
+      if (at < m) st.put(at, d2, idx);                    // (never beyond the m candidates the count pass found)
+    }
+    cnt += __popc(mk);
+  });
+  cnt = min(cnt, m);
+  st.publish();
+  int nk = 0;
+  for (int c0 = 0; c0 < cnt; c0 += 16) {
+    const int c = c0 + l;
+    bool keep = false;
+    int vj = 0;
+    if (c < cnt) {
+      const double vd = st.dist(c);
+      vj = st.id(c);
+      int below = 0;
+      for (int o = 0; o < cnt; o++) below += key_less(st.dist(o), st.id(o), vd, vj) ? 1 : 0;
+      keep = below < k;
+    }
+    const unsigned mk = (unsigned)((__ballot(keep) >> team_shift) & 0xffffu);
+    if (keep) {
+      const int at = nk + __popc(mk & below_l);
+      if (at < d) kept[at] = vj;
+    }
+    nk += __popc(mk);
+  }
+  return min(nk, d);
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256) void k_radius_capped_rows(int64_t n, int k, const double* __restrict__ X,
+                                                           const int32_t* __restrict__ point_cell, const int32_t* __restrict__ point_frame,
+                                                           const FrameGrid* __restrict__ frames, const int32_t* __restrict__ cell_start,
+                                                           const int32_t* __restrict__ sorted_idx, const double* __restrict__ sorted_pos,
+                                                           double r2, const int32_t* __restrict__ full, const int32_t* __restrict__ ptr,
+                                                           const int32_t* __restrict__ nbr_cache, double* __restrict__ spill_d,
+                                                           int32_t* __restrict__ spill_j, int64_t n_edges, int32_t* __restrict__ col,
+                                                           int64_t* __restrict__ edge_index) {
+  __shared__ double stage_d[16][CAPPED_LDS];
+  __shared__ int32_t stage_j[16][CAPPED_LDS];
+  __shared__ int32_t kept_lds[16][KNN_CAP];
+  const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const int l = threadIdx.x & 15;
+  if (i >= n) return;
+  const int m = full[i];
+  if (m == 0) return;
+  const int beg = ptr[i], d = ptr[i + 1] - beg;          // d = min(m, k)
+  const bool cut = m > d;
+  double q[DIM];
+#pragma unroll
+  for (int c = 0; c < DIM; c++) q[c] = X[i * DIM + c];
+  const EdgeWriter out{col, edge_index, n_edges, nullptr, 0};
+  auto emit = [&](int v, int rank) { if (rank < d) out.ids((int64_t)beg + rank, (int)i, v); };
+  if (m <= RADIUS_CACHE) {
+    // ---- the candidates are in the cache: lane l holds entries l, l + 16, l + 32
+    constexpr int SLOTS = (RADIUS_CACHE + 15) / 16;
+    int e[SLOTS], rk[SLOTS];
+    bool keep[SLOTS];
+#pragma unroll
+    for (int s_ = 0; s_ < SLOTS; s_++) {
+      keep[s_] = s_ * 16 + l < m;
+      e[s_] = keep[s_] ? nbr_cache[i * RADIUS_CACHE + s_ * 16 + l] : 0x7fffffff;
+      rk[s_] = 0;
+    }
+    if (cut) {                                            // keep the k smallest keys (d2, j)
+      double dd[SLOTS];
+      int below[SLOTS];
+#pragma unroll
+      for (int s_ = 0; s_ < SLOTS; s_++) {
+        dd[s_] = keep[s_] ? dist2<DIM>(q, X + (int64_t)e[s_] * DIM) : INFINITY;
+        below[s_] = 0;
+      }
+#pragma unroll
+      for (int s_ = 0; s_ < SLOTS; s_++) {
+        if (s_ * 16 >= m) break;
+        for (int c = 0; c < 16 && s_ * 16 + c < m; c++) {
+          const double vd = shfl16(dd[s_], c);
+          const int vj = __shfl(e[s_], c, 16);
+#pragma unroll
+          for (int u = 0; u < SLOTS; u++) below[u] += key_less(vd, vj, dd[u], e[u]) ? 1 : 0;
+        }
+      }
+#pragma unroll
+      for (int s_ = 0; s_ < SLOTS; s_++) keep[s_] = keep[s_] && below[s_] < k;
+    }
+    // an entry's place: the kept entries with a smaller id
+#pragma unroll
+    for (int s_ = 0; s_ < SLOTS; s_++) {
+      if (s_ * 16 >= m) break;
+      for (int c = 0; c < 16 && s_ * 16 + c < m; c++) {
+        const int v = __shfl(e[s_], c, 16);
+        const int vk = __shfl(keep[s_] ? 1 : 0, c, 16);
+#pragma unroll
+        for (int u = 0; u < SLOTS; u++) rk[u] += (vk && v < e[u]) ? 1 : 0;
+      }
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SLOTS; s_++)
+      if (keep[s_]) emit(e[s_], rk[s_]);
+    return;
+  }
+  // ---- beyond the cache: search again
+  const int team = threadIdx.x >> 4;
+  int32_t* const kept = kept_lds[team];
+  const FrameGrid g = frames[point_frame[i]];
+  const int cell = point_cell[i];
+  int nk;
+  if (!cut) {                                             // the whole row (m <= k <= KNN_CAP entries): ids straight into `kept`
+    int cnt = 0;
+    walk_cells_team<DIM>(q, (int)i, g, cell, cell_start, sorted_idx, sorted_pos, r2, l,
+                         [&](bool hit, int idx, double) { cnt += stage_hits(hit, idx, l, cnt, d, true, kept, nullptr); });
+    nk = min(cnt, d);
+  } else if (m <= CAPPED_LDS) {
+    nk = select_staged_row<DIM, true>(q, (int)i, g, cell, cell_start, sorted_idx, sorted_pos, r2, l, m, k, d,
+                                      StagedKeys<true>{stage_d[team], stage_j[team]}, kept);
+  } else {
+    const int64_t so = (int64_t)ptr[n + i] - (int64_t)ptr[n];   // the row's slice of the scratch: the second half of the scan
+    nk = select_staged_row<DIM, false>(q, (int)i, g, cell, cell_start, sorted_idx, sorted_pos, r2, l, m, k, d,
+                                       StagedKeys<false>{spill_d + so, spill_j + so}, kept);
+  }
+  rank_staged_row(true, kept, nullptr, nk, l, emit);
+}
+}  // namespace
+
+// The capped radius graph (see k_radius_capped_rows): count -> ONE scan over lens [2 n] (the caller's) -> rows.
+extern "C" int rgnn_radius_graph_capped_count(const rgnn_grid* g, double r, int32_t k, int32_t* full, int32_t* lens,
+                                              rgnn_stream_t stream) {
+  RGNN_CHECK_ARG(k >= 1 && k <= KNN_CAP, "k must be in [1, 128]");
+  RGNN_CHECK_ARG(g && (g->n == 0 || (full && lens)), "null full / lens");
+  int rc = launch_radius<false>(g, r, full, nullptr, nullptr, nullptr, 0, nullptr, nullptr, stream);
+  if (rc || g->n == 0) return rc;
+  hipLaunchKernelGGL(k_capped_lengths, dim3(rgnn_blocks(g->n, 256)), dim3(256), 0, (hipStream_t)stream, full, g->n, (int)k, lens);
+  RGNN_CHECK_LAUNCH();
+  return RGNN_OK;
+}
+
+extern "C" int rgnn_radius_graph_capped_rows(const rgnn_grid* g, double r, int32_t k, const int32_t* full, const int32_t* ptr,
+                                             int32_t* col, int64_t* edge_index, int64_t n_edges, void* spill, int64_t n_spill,
+                                             rgnn_stream_t stream) {
+  RGNN_CHECK_ARG(k >= 1 && k <= KNN_CAP, "k must be in [1, 128]");
+  RGNN_CHECK_ARG(n_edges >= 0 && n_spill >= 0, "negative sizes");
+  RGNN_CHECK_ARG(g && (g->n == 0 || (full && ptr && (col || n_edges == 0))), "null full / ptr / col");
+  int rc = check_grid(g);
+  if (rc) return rc;
+  if (g->n == 0 || n_edges == 0) return RGNN_OK;
+  RGNN_CHECK_ARG(n_spill == 0 || (spill != nullptr && ((uintptr_t)spill & 7) == 0), "null or misaligned spill (12 B x n_spill)");
+  GridView v = make_view(g->ws, g->n, g->n_frames, g->dim);
+  double* spill_d = (double*)spill;                         // [n_spill] distances, then [n_spill] ids
+  int32_t* spill_j = (int32_t*)(spill_d + n_spill);
+  RGNN_WITH_DIM(g->dim, hipLaunchKernelGGL(k_radius_capped_rows<DIM>, dim3(rgnn_blocks(g->n, 16)), dim3(256), 0, (hipStream_t)stream, g->n,
+                                           (int)k, g->X, v.point_cell, v.point_frame, v.frames, v.cell_start, v.sorted_idx, v.sorted_pos,
+                                           r * r, full, ptr, v.nbr_cache, spill_d, spill_j, n_edges, col, edge_index));
+  RGNN_CHECK_LAUNCH();
+  return RGNN_OK;
+}
+
 static int knn_grid_walk(const rgnn_grid* g, int32_t k, int32_t* nbr, int64_t* edge_index, int32_t* status,
                          float* relative_position, int32_t undirected, int32_t* degree_init, rgnn_stream_t stream);
 

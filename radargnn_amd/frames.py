@@ -36,6 +36,13 @@ class GraphSettings:
     edge_features: Sequence[str] = ("relative_position",)
     edge_mode: str = "directed"
     distance_definition: str = "X"               # "X" | "XV"
+    # radius graphs only: a point with more neighbours within r keeps the nearest max_neighbors (ops.radius_graph_capped); None: no
+    # cap.  The capped graph is not symmetric: none of the radius path's symmetric shortcuts apply, and it is not captured (HotPath)
+    max_neighbors: Optional[int] = None
+
+    @property
+    def capped(self) -> bool:
+        return self.algorithm == "radius" and self.max_neighbors is not None
 
 
 @dataclass
@@ -131,6 +138,12 @@ def _stage_search(batch: FrameBatch, cfg: GraphSettings, status: torch.Tensor, s
         return {"grid": grids[0], "nbr": res[0], "ei": res[1], "rel": res[3] if len(res) > 3 else None,
                 "deg0": res[4] if len(res) > 4 else None}
     if cfg.algorithm == "radius":
+        if cfg.capped:
+            # the whole search, its one host read included: nothing of a capped graph is known before its rows are (eager steps only)
+            grids: list = []
+            rowptr, col, ei = ops.radius_graph_capped(basis, batch.frame_ptr, cfg.r, cfg.max_neighbors, grid_out=grids,
+                                                      max_frame_points=biggest)
+            return {"grid": grids[0], "rowptr": rowptr, "col": col, "ei": ei}
         sdict = static if static is not None else {}
         if grid_only and static is not None and "grid" in static:
             return {"grid": ops.radius_grid(basis, batch.frame_ptr, cfg.r, static, max_frame_points=biggest), "rowptr": None, "deg": None}
@@ -175,6 +188,9 @@ def _stage_features(batch: FrameBatch, cfg: GraphSettings, status: torch.Tensor,
     if cfg.algorithm == "knn":
         ei, col, rowptr = st["ei"], st["nbr"].reshape(-1), None
         edge_attr_fused = st.get("rel")
+    elif cfg.capped:
+        ei, col, rowptr = st["ei"], st["col"], st["rowptr"]
+        rows_out = rowptr
     else:
         rowptr = st["rowptr"]
         rows_out = rowptr
@@ -220,6 +236,8 @@ def _stage_features(batch: FrameBatch, cfg: GraphSettings, status: torch.Tensor,
             csr = TargetCSR(ei, n, order=grid.cell_order(), rank=grid.cell_rank(), all_sources=True, status=status,
                             knn_frames=(batch.frame_ptr, cfg.k, int(batch.frame_sizes.max())), ordered=ordered_csr)
             degree = ops.knn_degree_from_csr(csr.rowptr, csr.src, csr.order, st["nbr"])
+        elif cfg.capped:
+            degree = ops.undirected_degree(rowptr, col, n)     # (i keeps j does not mean j keeps i: count both directions)
         elif cfg.algorithm == "radius":
             # d(i,j) <= r is symmetric, so the directed edge set is symmetric and the undirected degree networkx
             # reports (graph.py:93-96) is simply the out-degree the count pass already produced
@@ -247,7 +265,7 @@ def _stage_features(batch: FrameBatch, cfg: GraphSettings, status: torch.Tensor,
         # node-feature kernel counts them per frame on the way and one more launch compacts the two lists (TargetCSR would
         # otherwise spend four launches on them)
         per_frame = (torch.empty(batch.num_frames, dtype=torch.int32, device=dev)
-                     if (cfg.algorithm == "radius" and degree is not None and ops.SORTED_ROW_LISTS
+                     if (cfg.algorithm == "radius" and not cfg.capped and degree is not None and ops.SORTED_ROW_LISTS
                          and os.environ.get("RGNN_NO_FUSED_SPLIT") is None) else None)
         x = ops.node_features_time_index(batch.X, batch.V, batch.rcs, batch.timestamp, batch.frame_ptr, degree,
                                          list(cfg.node_features), dtype=torch.float32, status=status, frame_nonempty=per_frame)
@@ -275,6 +293,8 @@ def build_graphs(batch: FrameBatch, cfg: GraphSettings, ordered_csr: bool = True
     big = None
     if cfg.algorithm == "knn":
         n_edges = batch.num_points * cfg.k
+    elif cfg.capped:
+        n_edges = int(st["ei"].shape[1])
     else:
         n_edges, e_big = st["counts"].tolist()
         big = e_big / max(n_edges, 1)
@@ -306,13 +326,18 @@ class HotPath:
         # bn_scope = "frame": every train-mode BatchNorm takes its statistics per frame -- the numbers the reference's
         # one-frame-per-forward inference loop computes (evaluate.py:40; the model is never put in eval mode), at batched
         # throughput.  "batch": statistics over the whole batch, what ONE forward over a 64-frame Batch computes.
+        if graph_settings.capped:
+            ops.check_neighbor_cap(graph_settings.max_neighbors)
+            if use_hip_graphs:
+                raise ValueError("a capped radius graph (max_neighbors) runs eagerly only: its step is not captured yet")
         self.bn_scope = bn_scope
         self.model = model
         self.cfg = graph_settings
         self.with_softmax = with_softmax
         self.use_hip_graphs = use_hip_graphs
         # radius graphs hold (s, t) and (t, s) alike (|a - b|^2 is evaluated symmetrically); kNN graphs do not
-        self.symmetric_graph = graph_settings.algorithm == "radius"
+        # ... nor does a capped radius graph (i may keep j while j, in a denser place, drops i)
+        self.symmetric_graph = graph_settings.algorithm == "radius" and not graph_settings.capped
         # a maximum does not depend on the order of a target's in-edges: the CSR build of kNN batches skips its ranking pass
         # (inference only: see _ordered_csr)
         self._unordered_csr_ok = getattr(model, "aggregation", None) == "max" and os.environ.get("RGNN_ORDERED_CSR") is None
@@ -350,9 +375,9 @@ class HotPath:
         edge_side = g.edge_side if g.csr is None else None
         with torch.cuda.stream(edge_side):                      # (None: the current stream; else the edge side of a captured step)
             graph = g.csr if g.csr is not None else TargetCSR(g.edge_index, g.x.shape[0], order=g.cell_order, rank=g.cell_rank, symmetric=self.symmetric_graph,
-                              all_sources=self.cfg.algorithm == "knn", source_rows=g.rowptr, status=g.status, split=g.split,
+                              all_sources=self.cfg.algorithm == "knn", source_rows=g.rowptr if self.symmetric_graph else None, status=g.status, split=g.split,
                               knn_frames=((self._frame_ptr, self.cfg.k, self._biggest_frame) if self.cfg.algorithm == "knn" else None),
-                              own_edges=rel_only or twin_free, big_edge_fraction=g.big_edge_fraction, ordered=self._ordered_csr)
+                              own_edges=self.symmetric_graph and (rel_only or twin_free), big_edge_fraction=g.big_edge_fraction, ordered=self._ordered_csr)
             if graph.own_edge is not None and not rel_only:
                 ea_sorted = ops.edge_features_reversed(g.points[0], g.points[1], g.edge_index, graph.own_edge, list(self.cfg.edge_features),
                                                        self.cfg.edge_mode, dtype=g.edge_attr.dtype, status=g.status)[0]
@@ -399,6 +424,8 @@ class HotPath:
         is still running (r04: the host read stood between every batch's search and model stages, and the device idled while Python
         enqueued the ~45 launches of the model stage: 0.81 of the resident rate)."""
         _check_knn_sizes(batch, self.cfg)
+        if self.cfg.capped:
+            raise ValueError("a capped radius graph (max_neighbors) has no two-half step: its search reads its counts back itself")
         dev = batch.X.device
         side = ops.ctx().side(dev, "search")                     # (a hardware queue of its own: ops.independent_stream)
         with torch.cuda.stream(side):
@@ -517,6 +544,8 @@ class FrameStreamer:
     def __init__(self, hot: "HotPath", slots: int = 6, lookahead: bool = True, behind: int = 2):
         if slots < 2:
             raise ValueError("at least two staging slots")
+        if hot.cfg.capped:
+            raise ValueError("FrameStreamer does not stream capped radius graphs (max_neighbors) yet")
         self.hot = hot
         self.slots = slots
         self.behind = behind           # results are handed out this many batches late (clamped to slots - 1; see run)

@@ -73,9 +73,11 @@ class Graph:
     def A(self, value):
         self._A = value
 
-    def build(self, X: np.ndarray, routine: str, k: int = 6, r: float = 1) -> None:
+    def build(self, X: np.ndarray, routine: str, k: int = 6, r: float = 1, max_neighbors: Optional[int] = None) -> None:
         """Edges between the rows of ``X`` (all columns count for the distance); nothing happens for fewer than
-        two points or an unknown routine (graph.py:45-50)."""
+        two points or an unknown routine (graph.py:45-50).  ``max_neighbors`` (radius graphs; no reference counterpart): a point
+        with more neighbours within ``r`` keeps the nearest ``max_neighbors`` of them (ops.radius_graph_capped) -- the graph is
+        then no longer symmetric."""
         X = np.asarray(X)
         n = X.shape[0]
         if n <= 1 or routine not in ("knn", "radius"):
@@ -87,8 +89,10 @@ class Graph:
                 raise ValueError(f"Expected n_neighbors < n_samples_fit, but n_neighbors = {k}, "
                                  f"n_samples_fit = {n}, n_samples = {n}")
             _, ei, _ = ops.knn_graph(Xd, ptr, int(k))
-        else:
+        elif max_neighbors is None:
             _, _, ei = ops.radius_graph(Xd, ptr, float(r))
+        else:
+            _, _, ei = ops.radius_graph_capped(Xd, ptr, float(r), max_neighbors)
         self.E = np.ascontiguousarray(ei.t().to(torch.int32).cpu().numpy())
         self._A = None
         self._n_nodes = n
@@ -126,8 +130,8 @@ class GeometricGraph(Graph):
         self.V = None
         self.F = None
 
-    def build(self, X, routine, k: int = 6, r: float = 1) -> None:
-        super().build(X, routine, k=k, r=r)
+    def build(self, X, routine, k: int = 6, r: float = 1, max_neighbors: Optional[int] = None) -> None:
+        super().build(X, routine, k=k, r=r, max_neighbors=max_neighbors)
         if self._n_nodes is None and self.X is not None:
             self._n_nodes = np.asarray(self.X).shape[0]
 
@@ -242,7 +246,7 @@ def build_geometric_graph(config, point_cloud) -> GeometricGraph:
     graph.F = {"rcs": getattr(point_cloud, "rcs", None)}
     if "time_index" in config.node_features:
         graph.add_invariant_feature("time_index", time_index_of(point_cloud.timestamp))
-    graph.build(basis, config.graph_construction_algorithm, k=config.k, r=config.r)
+    graph.build(basis, config.graph_construction_algorithm, k=config.k, r=config.r, max_neighbors=getattr(config, "max_neighbors", None))
     graph.extract_node_pair_features(config.edge_features, config.edge_mode)
     graph.extract_single_node_features(config.node_features)
     return graph

@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import numbers
 import os
 import sys
 from typing import List, Optional, Sequence, Tuple
@@ -383,6 +384,45 @@ def radius_graph(X: torch.Tensor, frame_ptr: torch.Tensor, r: float, want_edge_i
     n_edges = int(rowptr[-1].item()) if n > 0 else 0
     col, ei = radius_graph_fill(g, rowptr, r, n_edges, want_edge_index)
     return rowptr, col, ei
+
+
+RADIUS_CAP_MAX = 128     # KNN_CAP of csrc/graph.hip
+
+
+def check_neighbor_cap(k) -> int:
+    """The cap of a capped radius graph as an int; ValueError unless it is an integer in [1, 128]."""
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+        raise ValueError(f"the neighbour cap must be an integer (got {type(k).__name__})")
+    if not 1 <= int(k) <= RADIUS_CAP_MAX:
+        raise ValueError(f"the neighbour cap must be in [1, {RADIUS_CAP_MAX}] (got {int(k)})")
+    return int(k)
+
+
+def radius_graph_capped(X: torch.Tensor, frame_ptr: torch.Tensor, r: float, k: int, want_edge_index: bool = True,
+                        grid_out: Optional[list] = None, max_frame_points: int = 0):
+    """The radius graph with at most ``k`` neighbours per point: a row of more than k entries keeps the k nearest -- smallest
+    (d2, j): distance asc, index asc, the order of ``knn_graph`` -- and every row is stored with ascending neighbour ids.
+    -> rowptr int32 [N+1], col int32 [E], edge_index int64 [2,E] like ``radius_graph``; equal to it, bit for bit, when no row is
+    longer than k.  NOT symmetric.  One device->host read (E and the size of the fill's scratch, side by side)."""
+    k = check_neighbor_cap(k)
+    g = GridHash(X, frame_ptr).build(cell_size=float(r) if r > 0 else 1e-300, max_frame_points=max_frame_points)
+    if grid_out is not None:
+        grid_out.append(g)
+    n, dev = g.n, X.device
+    full = torch.empty(n, dtype=torch.int32, device=dev)
+    lens = torch.empty(2 * n, dtype=torch.int32, device=dev)
+    check(lib.rgnn_radius_graph_capped_count(C.byref(g.desc), float(r), k, _ptr(full), _ptr(lens), _stream()))
+    ptr = exclusive_scan_i32(lens)                       # [2n + 1]: the rows, then the scratch slices behind E = ptr[n]
+    n_edges, end = ptr[n::n].tolist() if n > 0 else (0, 0)
+    if not 0 <= n_edges <= end:
+        raise RuntimeError("radius_graph_capped: more than 2^31 candidates in the batch")
+    col = torch.empty(n_edges, dtype=torch.int32, device=dev)
+    ei = torch.empty((2, n_edges), dtype=torch.int64, device=dev) if want_edge_index else None
+    n_spill = end - n_edges
+    spill = torch.empty(3 * n_spill, dtype=torch.int32, device=dev) if n_spill else None
+    check(lib.rgnn_radius_graph_capped_rows(C.byref(g.desc), float(r), k, _ptr(full), _ptr(ptr), _ptr(col), _ptr(ei), n_edges,
+                                            _ptr(spill), n_spill, _stream()))
+    return ptr[:n + 1], col, ei
 
 
 def knn_graph(X: torch.Tensor, frame_ptr: torch.Tensor, k: int, status: Optional[torch.Tensor] = None,

@@ -370,7 +370,8 @@ def graph_settings(graph_config) -> GraphSettings:
     return GraphSettings(algorithm=graph_config.graph_construction_algorithm, k=base.k if graph_config.k is None else int(graph_config.k),
                          r=base.r if graph_config.r is None else float(graph_config.r), node_features=tuple(graph_config.node_features),
                          edge_features=tuple(graph_config.edge_features), edge_mode=graph_config.edge_mode,
-                         distance_definition=graph_config.distance_definition)
+                         distance_definition=graph_config.distance_definition,
+                         max_neighbors=getattr(graph_config, "max_neighbors", None))
 
 
 def create_graph_data_from_sequence(table: SequenceTable, graph_config, dataset_config, sensor_yaw, label_map) -> list:
