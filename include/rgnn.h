@@ -308,7 +308,9 @@ int rgnn_node_features(const double* X, const double* V, const double* rcs, cons
                        int32_t out_is_f64, rgnn_stream_t stream);
 
 /* time_index[i] = rank of timestamp[i] among the sorted distinct timestamps of its frame
- * (radarscenes/dataset_creation.py:214-223, nuscenes/conversion.py:94-103). */
+ * (radarscenes/dataset_creation.py:214-223, nuscenes/conversion.py:94-103).  The timestamps must be NaN-free: the reference never
+ * produces one, and a NaN has no rank (it is also the bit pattern of an empty slot of the hash set).  A frame with more than 3 072
+ * distinct timestamps sets RGNN_STATUS_TIME_INDEX_OVERFLOW in *status; the time_index of that call is then not to be used. */
 int rgnn_time_index(const double* timestamp, const int64_t* frame_ptr, int64_t n_frames, double* time_index,
                     int32_t* status /*[dev]*/, rgnn_stream_t stream);
 /* rgnn_time_index for batches with LARGE frames (one 100 000-point cloud: one block per frame walks it alone in 160 us): the points
@@ -319,7 +321,9 @@ int rgnn_time_index_ws(const double* timestamp, const int64_t* frame_ptr, int64_
                        int32_t* status, void* ws /*[dev] rgnn_time_index_ws_bytes, 16-byte aligned*/, int64_t ws_bytes,
                        rgnn_stream_t stream);
 /* rgnn_time_index + rgnn_node_features in one launch (one block per frame): the time index of a point goes straight into its
- * column of the feature row; same values as the two calls (graph.py:225-275, dataset_creation.py:214-223). */
+ * column of the feature row; same values as the two calls (graph.py:225-275, dataset_creation.py:214-223).  frame_nonempty, when
+ * given, is ALWAYS filled for all n_frames frames (0 for an empty frame) -- also when there is no feature row to write (n == 0,
+ * where degree may be NULL, or an empty feature list) --, so rgnn_split_by_degree_frames never reads an unwritten count. */
 int rgnn_node_features_time_index(const double* X, const double* V, const double* rcs, const double* timestamp,
                                   const int64_t* frame_ptr, int64_t n_frames, const int32_t* degree /*[dev] or NULL*/, int64_t n,
                                   const int32_t* codes /*host*/, int32_t n_codes, void* out, int32_t out_is_f64,

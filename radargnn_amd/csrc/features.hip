@@ -372,6 +372,24 @@ __global__ __launch_bounds__(256) void k_ti_rank(const double* __restrict__ ts, 
   out[i] = (double)lo;
 }
 
+// frame_nonempty alone, for the calls of rgnn_node_features_time_index that have no feature row to write (no nodes, or an empty
+// feature list): one block per frame, 0 for an empty frame -- rgnn_split_by_degree_frames never reads an unwritten count.
+__global__ __launch_bounds__(256) void k_frame_nonempty(const int32_t* __restrict__ degree, const int64_t* __restrict__ frame_ptr,
+                                                       int32_t* __restrict__ frame_nonempty) {
+  __shared__ int nz_total;
+  const int f = blockIdx.x;
+  const int64_t beg = frame_ptr[f], end = frame_ptr[f + 1];
+  if (threadIdx.x == 0) nz_total = 0;
+  __syncthreads();
+  int nz = 0;
+  for (int64_t i = beg + threadIdx.x; i < end; i += blockDim.x) nz += degree[i] > 0 ? 1 : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) nz += __shfl_xor(nz, o, 64);
+  if ((threadIdx.x & 63) == 0 && nz) atomicAdd(&nz_total, nz);
+  __syncthreads();
+  if (threadIdx.x == 0) frame_nonempty[f] = nz_total;
+}
+
 int edge_width(const int32_t* codes, int n) {
   int w = 0;
   for (int i = 0; i < n; i++) {
@@ -711,14 +729,22 @@ extern "C" int rgnn_node_features_time_index(const double* X, const double* V, c
                                              const int64_t* frame_ptr, int64_t n_frames, const int32_t* degree, int64_t n,
                                              const int32_t* codes, int32_t n_codes, void* out, int32_t out_is_f64,
                                              int32_t* status, int32_t* frame_nonempty, rgnn_stream_t stream) {
-  RGNN_CHECK_ARG(frame_nonempty == nullptr || degree != nullptr, "frame_nonempty needs the degrees");
+  RGNN_CHECK_ARG(frame_nonempty == nullptr || degree != nullptr || n == 0, "frame_nonempty needs the degrees");
   RGNN_CHECK_ARG(n_codes >= 0 && n_codes <= RGNN_MAX_FEATURE_CODES && (n_codes == 0 || codes), "bad feature code list");
   const int width = node_width(codes, n_codes);
   if (width < 0) {
     rgnn_set_error("Invalid node feature specified");
     return RGNN_ERR_INVALID_ARGUMENT;
   }
-  if (n == 0 || width == 0 || n_frames == 0) return RGNN_OK;
+  if (n == 0 || width == 0 || n_frames == 0) {
+    // no feature row to write, but frame_nonempty is filled whenever it is given (degree is not read where every frame is empty)
+    if (frame_nonempty != nullptr && n_frames > 0) {
+      RGNN_CHECK_ARG(frame_ptr && n_frames < ((int64_t)1 << 31), "frame_nonempty needs frame_ptr");
+      hipLaunchKernelGGL(k_frame_nonempty, dim3((unsigned)n_frames), dim3(256), 0, (hipStream_t)stream, degree, frame_ptr, frame_nonempty);
+      RGNN_CHECK_LAUNCH();
+    }
+    return RGNN_OK;
+  }
   RGNN_CHECK_ARG(timestamp && frame_ptr && out && status, "null pointers");
   for (int i = 0; i < n_codes; i++) {
     RGNN_CHECK_ARG(codes[i] != RGNN_NF_RCS || rcs, "rcs requested but NULL");

@@ -659,6 +659,8 @@ def split_by_degree_frames(degree: torch.Tensor, frame_ptr: torch.Tensor, frame_
     slot = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     lst_ne = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     cnt_ne = torch.empty(1, dtype=torch.int64, device=dev)
+    if n == 0:                                     # (no node: nothing of `degree` is read, but the entry point refuses a null pointer)
+        degree = torch.zeros(1, dtype=torch.int32, device=dev)
     check(lib.rgnn_split_by_degree_frames(_ptr(degree), _ptr(frame_ptr.contiguous()), frame_ptr.numel() - 1, _ptr(frame_nonempty),
                                           _ptr(lst), _ptr(cnt), _ptr(slot), _ptr(lst_ne), _ptr(cnt_ne), _stream()))
     return lst, cnt, slot, lst_ne, cnt_ne
