@@ -459,6 +459,17 @@ int32_t rgnn_linear_planes_kp(int32_t k);
 int rgnn_linear_split_weights(const float* W1, const float* W2, int64_t ldw, int32_t w_split, int32_t n, int32_t k,
                               void* planes /*[dev] uint16, 3 n kp of them*/, rgnn_stream_t stream);
 int rgnn_linear_fwd(const rgnn_linear_args* args /*host*/, rgnn_stream_t stream);
+/* Two INDEPENDENT dense launches (neither reads what the other writes, their output rows are disjoint) handed over together:
+ * the same results, bit for bit, as rgnn_linear_fwd(second) followed by rgnn_linear_fwd(first) -- output rows, col_stats panels
+ * and out_absmax slots.  Where both are row-subset launches of the LDS-DMA kernel's f16x2 form on its static tile schedule (no
+ * per-segment tables, no residual / accumulate / gather_only, no use of splitk_ws whatever *m_dev holds) and their column-tile
+ * widths are a pair the library is built for (the conv layers' source term beside their isolated-row update: n = 464 | 224,
+ * 464 | 128, 272 | 64), they run as ONE grid: the launch with more tiles in front, the other one's work-groups starting on
+ * compute units as the first one's retire, instead of behind its last, partly filled tile round.  Neither part waits for the
+ * other.  Any other pair, RGNN_NO_LINEAR_PAIR in the environment, or armed profiling events (rgnn_profile_next_launch): the two
+ * launches.  rgnn_linear_fwd_pair_fuses: 1 if the pair would run as one grid (host-side, no launch). */
+int32_t rgnn_linear_fwd_pair_fuses(const rgnn_linear_args* first /*host*/, const rgnn_linear_args* second /*host*/);
+int rgnn_linear_fwd_pair(const rgnn_linear_args* first /*host*/, const rgnn_linear_args* second /*host*/, rgnn_stream_t stream);
 
 /* Three Linear layers back to back in one pass: out = act3(W3 relu(W2 relu(W1 x + b1) + b2) + b3) for k0 <= 8 inputs and layers
  * of 32, 64 and 128 columns -- DetNetBasic's node embedding (gnn_models.py:137-178, node_feature_embedding_layer_dimensions

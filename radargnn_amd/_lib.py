@@ -88,6 +88,8 @@ SIGNATURES = {
     "rgnn_time_index_ws": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "rgnn_linear_stat_panels": (c_i64, [c_i64]),
     "rgnn_linear_fwd": (c_i32, [C.POINTER(RgnnLinearArgs), c_vp]),
+    "rgnn_linear_fwd_pair": (c_i32, [C.POINTER(RgnnLinearArgs), C.POINTER(RgnnLinearArgs), c_vp]),
+    "rgnn_linear_fwd_pair_fuses": (c_i32, [C.POINTER(RgnnLinearArgs), C.POINTER(RgnnLinearArgs)]),
     "rgnn_linear_fwd_fuses_a1_affine": (c_i32, [C.POINTER(RgnnLinearArgs)]),
     "rgnn_linear_fwd_plan": (None, [C.POINTER(RgnnLinearArgs), C.POINTER(c_i32 * 8)]),
     "rgnn_linear_planes_kp": (c_i32, [c_i32]),

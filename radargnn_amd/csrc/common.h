@@ -55,6 +55,7 @@ extern std::atomic<int> g_rgnn_env_epoch;
 // point (rgnn_linear_fwd, rgnn_mpnn_aggregate) records immediately around its kernel launch, on the launch stream.
 void rgnn_prof_begin(hipStream_t s);
 void rgnn_prof_end(hipStream_t s);
+bool rgnn_prof_armed();   // events are waiting for the next instrumented launch (entry points that would merge launches do not)
 
 // hipFuncSetAttribute (dynamic LDS beyond 64 KB) is per DEVICE: a "done" flag per kernel and device, so that a process that drives
 // several GPUs sets it on each of them (r04 kept one flag per process -- right for the one-process-per-GPU launch contract only).

@@ -17,6 +17,7 @@ extern "C" void rgnn_profile_next_launch(void* ev_start, void* ev_stop) {
   g_ev_start = (hipEvent_t)ev_start;
   g_ev_stop = (hipEvent_t)ev_stop;
 }
+bool rgnn_prof_armed() { return g_ev_start != nullptr || g_ev_stop != nullptr; }
 void rgnn_prof_begin(hipStream_t s) {
   if (g_ev_start) { hipEventRecord(g_ev_start, s); g_ev_start = nullptr; }
 }

@@ -1078,6 +1078,28 @@ extern "C" int64_t rgnn_linear_stat_panels(int64_t m) { return (m + BM - 1) / BM
 // 256 work-group slots of 256 KiB (accumulators of a 256 x 256 tile) + one flag word each
 extern "C" int64_t rgnn_linear_splitk_ws_bytes(void) { return (int64_t)256 * 8 * 16 * 512 * 4 + 4096; }
 
+// The kernel parameters of a launch that follows plan `pl`
+static LinParams fill_params(const rgnn_linear_args* a, const LinearPlan& pl) {
+  const bool f16 = pl.family == RGNN_LINEAR_FAMILY_DMA && pl.form == RGNN_LINEAR_PATH_DMA_F16X2;
+  LinParams p;
+  p.A1 = a->A1; p.A2 = a->A2; p.lda1 = a->lda1; p.lda2 = a->lda2; p.k1 = a->k1; p.k2 = a->k2;
+  p.W1 = a->W1; p.W2 = a->W2; p.ldw = a->ldw; p.w_split = a->w_split >= a->n ? a->n : a->w_split;
+  p.bias1 = a->bias1; p.bias2 = a->bias2; p.residual = a->residual; p.ldr = a->ldr;
+  p.out = a->out; p.ldo = a->ldo; p.m = a->m; p.n = a->n; p.relu_out = a->relu_out; p.col_stats = a->col_stats;
+  p.mt = (int)((a->m + BM - 1) / BM); p.nt = pl.nt;
+  p.ext_a1 = pl.ext_a1; p.ext_a2 = pl.ext_a2; p.ext_w = pl.ext_w;
+  p.row_index = a->row_index; p.m_dev = a->m_dev; p.gather_only = a->gather_only; p.res_index = a->residual_index; p.accumulate = a->accumulate;
+  p.fast_epilogue = pl.fast_epilogue; p.direct_epilogue = pl.direct_epilogue; p.ext_out = pl.ext_out;
+  p.Wp = f16 ? a->W_planes_f16 : a->W_planes; p.kp = a->w_planes_kp; p.ext_wp = pl.ext_wp;
+  p.sk_ws = pl.split_k ? a->splitk_ws : nullptr;
+  p.sk_flags = pl.split_k ? (int*)((char*)a->splitk_ws + (int64_t)256 * 8 * 16 * 512 * 4) : nullptr;
+  p.no_split_k = pl.no_split_k; p.stagger = pl.stagger;
+  p.a1_aff = a->a1_scale_shift; p.a1_relu = a->a1_relu; p.a1_aff_panel = a->a1_panel_segment;
+  p.relu_lo = a->relu_from_col > 0 ? a->relu_from_col : 0;
+  p.fmt = f16 ? 1 : 0; p.a1_bound = a->a1_bound; p.a2_bound = a->a2_bound; p.out_absmax = a->out_absmax;
+  return p;
+}
+
 extern "C" int rgnn_linear_fwd(const rgnn_linear_args* a, rgnn_stream_t stream) {
   RGNN_CHECK_ARG(a != nullptr, "null args");
   RGNN_CHECK_ARG(a->m >= 0 && a->n >= 0 && a->k1 >= 0 && a->k2 >= 0, "negative sizes");
@@ -1111,23 +1133,7 @@ extern "C" int rgnn_linear_fwd(const rgnn_linear_args* a, rgnn_stream_t stream) 
     RGNN_CHECK_LAUNCH();
     return RGNN_OK;
   }
-  const bool f16 = pl.family == RGNN_LINEAR_FAMILY_DMA && pl.form == RGNN_LINEAR_PATH_DMA_F16X2;
-  LinParams p;
-  p.A1 = a->A1; p.A2 = a->A2; p.lda1 = a->lda1; p.lda2 = a->lda2; p.k1 = a->k1; p.k2 = a->k2;
-  p.W1 = a->W1; p.W2 = a->W2; p.ldw = a->ldw; p.w_split = a->w_split >= a->n ? a->n : a->w_split;
-  p.bias1 = a->bias1; p.bias2 = a->bias2; p.residual = a->residual; p.ldr = a->ldr;
-  p.out = a->out; p.ldo = a->ldo; p.m = a->m; p.n = a->n; p.relu_out = a->relu_out; p.col_stats = a->col_stats;
-  p.mt = (int)((a->m + BM - 1) / BM); p.nt = pl.nt;
-  p.ext_a1 = pl.ext_a1; p.ext_a2 = pl.ext_a2; p.ext_w = pl.ext_w;
-  p.row_index = a->row_index; p.m_dev = a->m_dev; p.gather_only = a->gather_only; p.res_index = a->residual_index; p.accumulate = a->accumulate;
-  p.fast_epilogue = pl.fast_epilogue; p.direct_epilogue = pl.direct_epilogue; p.ext_out = pl.ext_out;
-  p.Wp = f16 ? a->W_planes_f16 : a->W_planes; p.kp = a->w_planes_kp; p.ext_wp = pl.ext_wp;
-  p.sk_ws = pl.split_k ? a->splitk_ws : nullptr;
-  p.sk_flags = pl.split_k ? (int*)((char*)a->splitk_ws + (int64_t)256 * 8 * 16 * 512 * 4) : nullptr;
-  p.no_split_k = pl.no_split_k; p.stagger = pl.stagger;
-  p.a1_aff = a->a1_scale_shift; p.a1_relu = a->a1_relu; p.a1_aff_panel = a->a1_panel_segment;
-  p.relu_lo = a->relu_from_col > 0 ? a->relu_from_col : 0;
-  p.fmt = f16 ? 1 : 0; p.a1_bound = a->a1_bound; p.a2_bound = a->a2_bound; p.out_absmax = a->out_absmax;
+  const LinParams p = fill_params(a, pl);
   rgnn_prof_begin(s);
   if (pl.family == RGNN_LINEAR_FAMILY_DMA) {
     rgnn_linear_dma_launch(&p, pl.tn, pl.x3_subset, s);
@@ -1157,6 +1163,61 @@ extern "C" int rgnn_linear_fwd(const rgnn_linear_args* a, rgnn_stream_t stream) 
     launch<32, 4, 1, 1, 1>(p, pl.vec, pl.bufl, s);
   }
   rgnn_prof_end(s);
+  RGNN_CHECK_LAUNCH();
+  return RGNN_OK;
+}
+
+// linear_dma.hip: is k_linear_dma_pair built for these two column-tile widths (in this order), and its launch
+int rgnn_linear_dma_pair_built(int tn_first, int tn_second);
+void rgnn_linear_dma_launch_pair(const void* first, int tn_first, const void* second, int tn_second, hipStream_t s);
+
+// Does the LDS-DMA kernel deal this launch's tiles whole (the static schedule) WHATEVER row count its m_dev holds?  It hands tiles over
+// (stream-K) or cuts their k-loops (parallel split-K) only with the workspace and from eight k-steps on (the f16x2 form's steps are
+// 32 k); stream-K only with one column tile, parallel split-K only on tiles of at most 128 columns.
+static bool dma_static_schedule(const LinearPlan& pl, const rgnn_linear_args* a) {
+  const int nk = (a->k1 + a->k2 + 31) / 32;
+  if (!pl.split_k || nk < 8) return true;
+  return pl.nt > 1 && (pl.tn > 4 || pl.no_split_k);
+}
+
+// One half of a pair that k_linear_dma_pair can take: a row-subset launch of the f16x2 form on the static schedule, one A1 table
+// at most (applied by the kernel), nothing the kernel's other schedules or epilogues would be needed for
+static bool pair_part(const LinearPlan& pl, const rgnn_linear_args* a) {
+  return pl.family == RGNN_LINEAR_FAMILY_DMA && pl.form == RGNN_LINEAR_PATH_DMA_F16X2 && pl.x3_subset &&
+         a->a1_panel_segment == nullptr && a->residual == nullptr && !a->accumulate && !a->gather_only &&
+         (a->a1_scale_shift == nullptr || pl.affine_batch) && dma_static_schedule(pl, a);
+}
+
+// 0: two launches; 1: one launch, `first` in front; 2: one launch, `second` in front (the part with more tiles leads: the other
+// one's work-groups start in the tail of its last tile round).  Host arithmetic on the argument values, like plan_linear.
+static int plan_pair(const rgnn_linear_args* first, const rgnn_linear_args* second, LinearPlan& plf, LinearPlan& pls) {
+  if (first == nullptr || second == nullptr || RGNN_ENV("RGNN_NO_LINEAR_PAIR") != nullptr) return 0;
+  plf = plan_linear(first);
+  pls = plan_linear(second);
+  if (!pair_part(plf, first) || !pair_part(pls, second)) return 0;
+  // (independent launches only: one grid gives no order between its parts)
+  if (first->out == second->A1 || first->out == second->A2 || second->out == first->A1 || second->out == first->A2) return 0;
+  const int64_t tiles_f = (first->m + 255) / 256 * plf.nt, tiles_s = (second->m + 255) / 256 * pls.nt;
+  if (tiles_s > tiles_f) return rgnn_linear_dma_pair_built(pls.tn, plf.tn) ? 2 : 0;
+  return rgnn_linear_dma_pair_built(plf.tn, pls.tn) ? 1 : 0;
+}
+
+extern "C" int32_t rgnn_linear_fwd_pair_fuses(const rgnn_linear_args* first, const rgnn_linear_args* second) {
+  LinearPlan plf, pls;
+  return plan_pair(first, second, plf, pls) != 0 ? 1 : 0;
+}
+
+extern "C" int rgnn_linear_fwd_pair(const rgnn_linear_args* first, const rgnn_linear_args* second, rgnn_stream_t stream) {
+  LinearPlan plf, pls;
+  // (armed profiling events time ONE launch: per-launch figures keep their meaning)
+  const int order = rgnn_prof_armed() ? 0 : plan_pair(first, second, plf, pls);
+  if (order == 0) {
+    const int rc = rgnn_linear_fwd(second, stream);
+    return rc != RGNN_OK ? rc : rgnn_linear_fwd(first, stream);
+  }
+  const LinParams pf = fill_params(first, plf), ps = fill_params(second, pls);
+  if (order == 1) rgnn_linear_dma_launch_pair(&pf, plf.tn, &ps, pls.tn, (hipStream_t)stream);
+  else rgnn_linear_dma_launch_pair(&ps, pls.tn, &pf, plf.tn, (hipStream_t)stream);
   RGNN_CHECK_LAUNCH();
   return RGNN_OK;
 }

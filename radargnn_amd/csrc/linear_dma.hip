@@ -122,8 +122,11 @@ typedef short raw16x8 __attribute__((ext_vector_type(8)));   // eight 16-bit ope
 //   kernels that produced them: |A| 2^sa < 2^15); the epilogue multiplies the accumulator by 2^-(sa + sw).  With the bound
 //   at 2^15 an element keeps all 22 bits while it is >= 2^-3 (its l is a normal f16 number), smaller ones are off by at most
 //   2^-25 in the scaled domain = 2^-40 of the bound -- a bound 2^19 above the tensor's typical magnitude still costs nothing.
+// The body takes its place in the launch as arguments (work-group `bid` of `nblocks`): k_linear_dma passes the grid's own numbers,
+// k_linear_dma_pair (below) those of the part the work-group belongs to.
 template <int TN, bool IDX, int FMT, int WV = 8>
-__global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
+// (unsigned like blockIdx.x / gridDim.x themselves: the expressions below then have the types they had on the builtins)
+__device__ __forceinline__ void linear_dma_body(const LinParams& p, const unsigned bid, const unsigned nblocks) {
   constexpr int BN = 32 * TN;
   constexpr int DMA_BM = 32 * WV;                  // rows per work-group tile
   constexpr int DMA_THREADS = 64 * WV;
@@ -157,7 +160,7 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
 
   const int64_t M = (IDX && p.m_dev) ? *p.m_dev : p.m;
   const int mt = (int)((M + DMA_BM - 1) / DMA_BM);
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, g8 = gridDim.x >> 3;
+  const int xcd = bid & 7, slot = bid >> 3, g8 = nblocks >> 3;
   const int my_panels = (mt > xcd) ? (mt - xcd + 7) / 8 : 0;
   const int n_items = my_panels * p.nt;
   const int t = threadIdx.x, lane = t & 63;
@@ -723,29 +726,75 @@ __global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
       float m = stat_lds[0];
 #pragma unroll
       for (int w = 1; w < WV; w++) m = fmaxf(m, stat_lds[w]);
-      bound_raise(p.out_absmax, blockIdx.x, m);
+      bound_raise(p.out_absmax, bid, m);
     }
   }
+}
+
+template <int TN, bool IDX, int FMT, int WV = 8>
+__global__ __launch_bounds__(64 * WV) void k_linear_dma(const LinParams p) {
+  linear_dma_body<TN, IDX, FMT, WV>(p, blockIdx.x, gridDim.x);
+}
+
+// TWO row-subset launches of the f16x2 eight-wave form in ONE grid: work-groups [0, split) are launch A's, numbered as if A had been
+// launched alone with `split` work-groups, the rest are launch B's.  The parts exchange nothing and neither waits for the other; a
+// work-group does exactly the tiles its number would do in a launch of its own (same bits, same statistics panels, same bound
+// slots).  What the single grid fixes is the ORDER: the hardware hands out work-groups by ascending blockIdx, so B's start on CUs as
+// A's retire, in the tail of A's last, partly filled tile round.  Static tile schedules only: the hand-over schedules share one
+// workspace (launch_dma_pair hands both parts over without it).  `split` is a multiple of 8, so block & 7 stays a part's XCD number.
+template <int TNA, int TNB>
+__global__ __launch_bounds__(512) void k_linear_dma_pair(const LinParams pa, const LinParams pb, const int split) {
+  if (blockIdx.x < (unsigned)split) linear_dma_body<TNA, true, 1, 8>(pa, blockIdx.x, (unsigned)split);
+  else linear_dma_body<TNB, true, 1, 8>(pb, blockIdx.x - (unsigned)split, gridDim.x - (unsigned)split);
+}
+
+// Tile counts of a launch (into p) and its grid: one 8-wave work-group per CU, or two of four waves
+template <int TN, int WV>
+int64_t dma_grid(LinParams& p) {
+  constexpr int BN = 32 * TN, DMA_BM = 32 * WV;
+  p.nt = (p.n + BN - 1) / BN;
+  p.mt = (int)((p.m + DMA_BM - 1) / DMA_BM);
+  const int64_t tiles = (int64_t)p.mt * p.nt;
+  int64_t grid = 256 * (8 / WV);
+  if (grid > tiles && (TN > 4 || p.sk_ws == nullptr || p.no_split_k || 2 * tiles > grid)) grid = tiles;   // (else: parallel split-K)
+  return (grid + 7) / 8 * 8;
+}
+inline size_t dma_aff_lds_bytes(const LinParams& p) {   // the A1 scale / shift tables behind the tiles: one, or two resident ones
+  return p.a1_aff ? (size_t)(p.a1_aff_panel ? 2 : 1) * RGNN_AFFINE_ROWS * 4 * p.k1 : 0;
 }
 
 template <int TN, bool IDX, int FMT, int WV = 8>
 void launch_dma(LinParams p, hipStream_t s) {
   constexpr int BN = 32 * TN;
   constexpr int NPL = FMT ? 2 : 3;
-  constexpr int DMA_BM = 32 * WV, DMA_THREADS = 64 * WV;
-  const size_t lds = (size_t)dma_lds_bytes(BN, NPL, WV) + (p.a1_aff ? (size_t)(p.a1_aff_panel ? 2 : 1) * RGNN_AFFINE_ROWS * 4 * p.k1 : 0);
-  p.nt = (p.n + BN - 1) / BN;
-  p.mt = (int)((p.m + DMA_BM - 1) / DMA_BM);
-  const int64_t tiles = (int64_t)p.mt * p.nt;
-  int64_t grid = 256 * (8 / WV);                   // one 8-wave work-group per CU, or two of four waves
-  if (grid > tiles && (TN > 4 || p.sk_ws == nullptr || p.no_split_k || 2 * tiles > grid)) grid = tiles;   // (else: parallel split-K)
-  grid = (grid + 7) / 8 * 8;
+  constexpr int DMA_THREADS = 64 * WV;
+  const size_t lds = (size_t)dma_lds_bytes(BN, NPL, WV) + dma_aff_lds_bytes(p);
+  const int64_t grid = dma_grid<TN, WV>(p);
   static RgnnOncePerDevice attr_once;
   if (attr_once.first()) {                                  // (room for the optional scale / shift table of the A1 operand: up to 1 024 columns)
     const int most = dma_lds_bytes(BN, NPL, WV) + 12288 < LDS_BYTES ? dma_lds_bytes(BN, NPL, WV) + 12288 : LDS_BYTES;
     hipFuncSetAttribute((const void*)k_linear_dma<TN, IDX, FMT, WV>, hipFuncAttributeMaxDynamicSharedMemorySize, most);
   }
   hipLaunchKernelGGL((k_linear_dma<TN, IDX, FMT, WV>), dim3((unsigned)grid), dim3(DMA_THREADS), lds, s, p);
+}
+
+// Both parts get the grid they would get alone (from their own arguments, workspace included), then go without the hand-over
+// workspace: the caller has established that neither would use it, and two parts must never meet in its slots.
+template <int TNA, int TNB>
+void launch_dma_pair(LinParams pa, LinParams pb, hipStream_t s) {
+  const size_t lds_a = (size_t)dma_lds_bytes(32 * TNA, 2, 8) + dma_aff_lds_bytes(pa);
+  const size_t lds_b = (size_t)dma_lds_bytes(32 * TNB, 2, 8) + dma_aff_lds_bytes(pb);
+  const int64_t split = dma_grid<TNA, 8>(pa), rest = dma_grid<TNB, 8>(pb);
+  pa.sk_ws = pb.sk_ws = nullptr;
+  pa.sk_flags = pb.sk_flags = nullptr;
+  static RgnnOncePerDevice attr_once;
+  if (attr_once.first()) {
+    const int tiles = dma_lds_bytes(32 * TNA, 2, 8) > dma_lds_bytes(32 * TNB, 2, 8) ? dma_lds_bytes(32 * TNA, 2, 8) : dma_lds_bytes(32 * TNB, 2, 8);
+    hipFuncSetAttribute((const void*)k_linear_dma_pair<TNA, TNB>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                        tiles + 12288 < LDS_BYTES ? tiles + 12288 : LDS_BYTES);
+  }
+  hipLaunchKernelGGL((k_linear_dma_pair<TNA, TNB>), dim3((unsigned)(split + rest)), dim3(512), lds_a > lds_b ? lds_a : lds_b, s, pa, pb,
+                     (int)split);
 }
 
 }  // namespace
@@ -826,4 +875,26 @@ void rgnn_linear_dma_launch(const void* params, int tn, int subset, hipStream_t 
       else { if (subset) launch_dma<8, true, 0>(p, s); else launch_dma<8, false, 0>(p, s); }
   }
 #undef RGNN_DMA
+}
+
+// The (first, second) column-tile widths k_linear_dma_pair is instantiated for: the ones the conv layers of the shipped widths
+// produce (source term, then isolated-row update: N = 464 | 224, 464 | 128, 272 | 64).  Any other pair runs as two launches.
+#define RGNN_DMA_PAIRS(X) X(5, 7) X(5, 4) X(3, 2)
+int rgnn_linear_dma_pair_built(int tn_first, int tn_second) {
+  const char* waves_e = RGNN_ENV("RGNN_DMA_WAVES");          // (the pair is the eight-wave form)
+  if (waves_e && atoi(waves_e) == 4) return 0;
+#define RGNN_DMA_PAIR(A, B) if (tn_first == A && tn_second == B) return 1;
+  RGNN_DMA_PAIRS(RGNN_DMA_PAIR)
+#undef RGNN_DMA_PAIR
+  return 0;
+}
+
+// Called by rgnn_linear_fwd_pair (linear.hip) once it has established that both launches are row-subset launches of the f16x2
+// eight-wave form on the static tile schedule, without per-segment tables, and that the pair is built.
+void rgnn_linear_dma_launch_pair(const void* first, int tn_first, const void* second, int tn_second, hipStream_t s) {
+  const LinParams& pa = *(const LinParams*)first;
+  const LinParams& pb = *(const LinParams*)second;
+#define RGNN_DMA_PAIR(A, B) if (tn_first == A && tn_second == B) return launch_dma_pair<A, B>(pa, pb, s);
+  RGNN_DMA_PAIRS(RGNN_DMA_PAIR)
+#undef RGNN_DMA_PAIR
 }

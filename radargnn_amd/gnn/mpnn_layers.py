@@ -707,6 +707,13 @@ class MPNNConv(_ConvBase):
         # update (K = C + D), isolated targets (m = 0) the plain W_px x + b_post (K = C).  The second one needs x
         # only; optionally (ISO_SIDE_STREAM) it runs on a side stream beside the source-term GEMM and the edge kernel.
         h = torch.empty((n, wcomb.shape[0]), dtype=torch.float32, device=x.device)
+        src_rows = graph.source_rows()
+        if frames is not None:
+            src_rows = (lst_ne, cnt_ne)                 # (symmetric graph: the sources are the targets with edges)
+        # The isolated-row launch and the source term read x only and write different matrices: handed over TOGETHER
+        # (ops.linear_pair) they run as one grid where the library has that pair, the isolated rows' work-groups starting in the
+        # tail of the source term's last tile round; RGNN_NO_LINEAR_PAIR=1, a profiler or another pair: the two launches below.
+        paired = frames is None and not ISO_SIDE_STREAM and src_rows is not None and ops.ctx().profiler is None
         if ISO_SIDE_STREAM:
             side = _side_stream(x.device)
             side.wait_stream(torch.cuda.current_stream())
@@ -714,13 +721,15 @@ class MPNNConv(_ConvBase):
             if side is not None:
                 with ops.no_splitk_workspace():                       # (may overlap main-stream launches that use the scratch)
                     ops.linear(x, w_iso, b_iso, out=h, row_index=lst_e, m_dev=cnt_e, stats_out=iso_stats, a1_affine=x_affine)
-            else:
+            elif not paired:
                 ops.linear(x, w_iso, b_iso, out=h, row_index=lst_e, m_dev=cnt_e, stats_out=iso_stats, a1_affine=x_affine,
                            a1_affine_tiles=tiles_e, padded_row_list=frames is not None)
-        src_rows = graph.source_rows()
-        if frames is not None:
-            src_rows = (lst_ne, cnt_ne)                 # (symmetric graph: the sources are the targets with edges)
-        if src_rows is not None:
+        if paired:
+            Q, _ = ops.linear_pair(
+                dict(a1=x, w1=w_src, row_index=src_rows[0], m_dev=src_rows[1], a1_affine=x_affine,
+                     out=ops.padded_rows(n, w_src.shape[0], x.device)),
+                dict(a1=x, w1=w_iso, bias1=b_iso, out=h, row_index=lst_e, m_dev=cnt_e, stats_out=iso_stats, a1_affine=x_affine))
+        elif src_rows is not None:
             # source term only on the nodes that have outgoing edges: nothing gathers the other rows of Q
             Q = ops.linear(x, w_src, row_index=src_rows[0], m_dev=src_rows[1], a1_affine=x_affine, a1_affine_tiles=tiles_ne,
                            padded_row_list=frames is not None, out=ops.padded_rows(n, w_src.shape[0], x.device))

@@ -931,7 +931,7 @@ def linear(a1: torch.Tensor, w1: torch.Tensor, bias1: Optional[torch.Tensor] = N
            stats_out: Optional[torch.Tensor] = None, gather_only: bool = False,
            residual_index: Optional[torch.Tensor] = None, cache_planes: bool = True,
            a1_affine: Optional[torch.Tensor] = None, a1_relu: bool = True, relu_from: int = 0,
-           a1_affine_tiles: Optional[torch.Tensor] = None, padded_row_list: bool = False):
+           a1_affine_tiles: Optional[torch.Tensor] = None, padded_row_list: bool = False, _held: Optional[list] = None):
     """out = act([a1|a2] @ [w1;w2]^T + [bias1;bias2]) (+ residual).  ``w1`` [n1, k1+k2] and ``w2`` [n2, k1+k2] may be
     column views of a larger weight (row stride = ldw).  Returns out or (out, col_stats).
     ``a1_affine`` float32 [AFFINE_ROWS, k1] (rows mean_hi, g, t of ``batchnorm_finalize``): the layer's first input block is
@@ -1063,8 +1063,11 @@ def linear(a1: torch.Tensor, w1: torch.Tensor, bias1: Optional[torch.Tensor] = N
         if word is None:
             word = ctx().bounds.word()
         args.out_absmax = _ptr(word)
-    tok = ctx().profiler.begin("linear") if ctx().profiler is not None else None
-    check(lib.rgnn_linear_fwd(C.byref(args), _stream()))
+    tok = ctx().profiler.begin("linear") if ctx().profiler is not None and _held is None else None
+    if _held is not None:
+        _held.append(args)                                # (linear_pair: everything but the launch, which it issues for both)
+    else:
+        check(lib.rgnn_linear_fwd(C.byref(args), _stream()))
     set_bound(out, word)                                  # (a launch that does not track invalidates an older bound)
     if row_index is not None and word is None:
         out._rgnn_rows_without_bound = True
@@ -1074,6 +1077,35 @@ def linear(a1: torch.Tensor, w1: torch.Tensor, bias1: Optional[torch.Tensor] = N
     if tok is not None:
         ctx().profiler.end(tok, m=m if m_dev is None else m_dev, n=n, k=k1 + k2, x3=planes is not None, f16=f16)   # row subsets: true count lives on the device
     return (out, stats) if (want_stats or stats_out is not None) else out
+
+
+
+def linear_pair(first: dict, second: dict):
+    """Two independent ``linear`` calls (keyword arguments as dicts; neither reads what the other writes, their output rows are
+    disjoint) handed to the library together (rgnn_linear_fwd_pair): where both are row-subset launches of the f16x2 dense form and
+    their widths are a pair the library is built for -- a conv layer's source term beside its isolated-row update -- they run as
+    ONE grid, the second one's work-groups starting as the first one's retire; otherwise, with a profiler in ``ctx()`` or with
+    RGNN_NO_LINEAR_PAIR=1 (read by the library: ``reload_env`` after changing it) as two launches, ``second`` first.  Same bits
+    either way.  Returns (result of first, result of second)."""
+    if ctx().profiler is not None:
+        r2 = linear(**second)
+        return linear(**first), r2
+    held = []
+    r2 = linear(**second, _held=held)
+    r1 = linear(**first, _held=held)
+    check(lib.rgnn_linear_fwd_pair(C.byref(held[1]), C.byref(held[0]), _stream()))
+    if lib.rgnn_linear_fwd_pair_fuses(C.byref(held[1]), C.byref(held[0])):
+        COUNTERS["linear_pair"] = COUNTERS.get("linear_pair", 0) + 1
+    return r1, r2
+
+
+def linear_pair_fuses(first: dict, second: dict) -> bool:
+    """Would ``linear_pair`` run these two calls as one grid (rgnn_linear_fwd_pair_fuses)?  No dense launch; everything else
+    ``linear`` does in front of its launch happens (weight planes, a bound word for the result)."""
+    held = []
+    linear(**second, _held=held)
+    linear(**first, _held=held)
+    return bool(lib.rgnn_linear_fwd_pair_fuses(C.byref(held[1]), C.byref(held[0])))
 
 
 def embed3(x: torch.Tensor, w1, b1, w2, b2, w3, b3, relu3: bool) -> Optional[torch.Tensor]:
