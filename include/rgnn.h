@@ -1206,6 +1206,42 @@ int rgnn_adam_step(int64_t n_tensors, void* const* param, const void* const* gra
 int rgnn_adapt_orientation_angle(const float* y, int64_t ldy, float* out, int64_t ldo, int64_t n, int32_t width,
                                  rgnn_stream_t stream);
 
+/* ---------------------------------------------------------------- rigid motions (csrc/transform.hip)
+ * The motion of frame (graph) f: p' = R(a_f) p + t_f for points, v' = R(a_f) v for velocities and differences, R = [[c, -s], [s, c]],
+ * angle[f] = a_f in radians, counter-clockwise, shift[f] = t_f; angle float64 [B], shift float64 [B, 2], both on the device.
+ * Everything is evaluated in double from the stored operands (separate multiplies and adds) and rounded once at the store.  An
+ * angle of exactly 0 keeps every rotated quantity bit for bit, a shift component of exactly 0 is not added: the identity motion
+ * returns the input bits.  One launch each, no temporaries, no host read.
+ *
+ * rgnn_rigid_points: X, V float64 [n, 2] -> X_out, V_out (V and V_out may both be NULL); row i belongs to the frame f with
+ * frame_ptr[f] <= i < frame_ptr[f + 1] (int64 [n_frames + 1]; frames of no rows are legal).  Out of place.
+ *
+ * rgnn_rigid_graph_nodes: the node rows of a collated batch; batch int64 [n] = the graph of every row.  pos / vel float32 [n, 2]
+ * -> pos_out / vel_out, whole rows, out of place.  x (row stride ldx, columns as the node feature codes list them) and y =
+ * [label | box] (row stride ldy, box_width 4 or 5): the caller passes COPIES as x_out / y_out and the kernel writes only what
+ * moves -- spatial_coordinates (moved as a point), velocity_vector (rotated); of a rotated box [c0, c1, l, w, theta] (box_width 5,
+ * theta in [0, pi)) with invariance 0 (none) the centre as a point, with invariance 1 (translation) the offset c - p rotated, and
+ * theta' = theta + a folded into [0, pi) in double, a result that rounds to float32(pi) stored as 0.  Rows whose first box column
+ * is NaN (background), the en encoding (2), aligned boxes (box_width 4), the label and every other feature are never written.
+ * Any of the pairs pos, vel, x, y may be NULL.
+ *
+ * rgnn_rigid_graph_edges: edge_attr (row stride lda, columns as the edge feature codes list them), `out` a COPY of it; the graph
+ * of edge e is batch[edge_index[0, e]].  relative_position / relative_velocity: directed -- the stored 2-vector rotated;
+ * undirected -- |R (q_i - q_j)| per component from the batch's ORIGINAL pos / vel float32 [n, 2], i = edge_index[0, e],
+ * j = edge_index[1, e].  Nothing else is written; edges of a graph whose angle is 0, or with an end outside [0, n), keep their
+ * rows. */
+int rgnn_rigid_points(const double* X, const double* V, const int64_t* frame_ptr, int64_t n, int64_t n_frames, const double* angle,
+                      const double* shift, double* X_out, double* V_out, rgnn_stream_t stream);
+int rgnn_rigid_graph_nodes(const float* pos, const float* vel, const float* x, int64_t ldx, const int32_t* node_codes /*host*/,
+                           int32_t n_codes, const float* y, int64_t ldy, int32_t box_width, int32_t invariance,
+                           const int64_t* batch, int64_t n, int64_t n_graphs, const double* angle, const double* shift,
+                           float* pos_out, float* vel_out, float* x_out, int64_t ldxo, float* y_out, int64_t ldyo,
+                           rgnn_stream_t stream);
+int rgnn_rigid_graph_edges(const float* edge_attr, int64_t lda, const int32_t* edge_codes /*host*/, int32_t n_codes,
+                           int32_t undirected, const int64_t* edge_index, int64_t n_edges, const int64_t* batch, int64_t n,
+                           int64_t n_graphs, const double* angle, const float* pos, const float* vel, float* out, int64_t ldo,
+                           rgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

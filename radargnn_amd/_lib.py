@@ -215,6 +215,11 @@ SIGNATURES = {
     "rgnn_adam_capacity": (c_i32, []),
     "rgnn_adam_step": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, C.POINTER(c_i32), c_vp]),
     "rgnn_adapt_orientation_angle": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp]),
+    "rgnn_rigid_points": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_rigid_graph_nodes": (c_i32, [c_vp, c_vp, c_vp, c_i64, C.POINTER(c_i32), c_i32, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_i64,
+                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "rgnn_rigid_graph_edges": (c_i32, [c_vp, c_i64, C.POINTER(c_i32), c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp,
+                                       c_vp, c_i64, c_vp]),
 }
 
 
