@@ -57,6 +57,11 @@ typedef void* rgnn_stream_t; /* hipStream_t */
 #define RGNN_STATUS_NUSC_BAD_BOX_PTR 1024    /* rgnn_nusc_boxes / rgnn_nusc_label_points: a sample's box offsets do not lie inside the box
                                               * list (the sample is treated as one without boxes) */
 
+#define RGNN_STATUS_DBSCAN_FRAME_TOO_LARGE 2048 /* rgnn_dbscan_labels: a frame of more than rgnn_dbscan_max_frame_points() points; its rows get
+                                              * label -1 and core 0, its n_clusters 0 */
+#define RGNN_STATUS_DBSCAN_BAD_ROW 4096      /* rgnn_dbscan_labels: an entry of col outside its row's frame (skipped), a row whose offsets do
+                                              * not lie inside [0, n_edges] (taken as empty) or a frame outside the points (left unwritten) */
+
 #define RGNN_SPLITK_TIMEOUT_WORD 1000    /* index of the time-out counter in the flag area of rgnn_linear_args.splitk_ws */
 
 const char* rgnn_version(void);
@@ -1031,6 +1036,44 @@ int32_t rgnn_gt_object_cap(void);
 int rgnn_create_gt_boxes(const double* pos, int64_t n, const int64_t* obj_ptr, const int32_t* obj_rows, int64_t n_rows,
                          int64_t n_obj, const int32_t* nn_index /*[dev] or NULL*/, int32_t aligned, int32_t invariance,
                          double* out, double* rect /*[dev] or NULL*/, int32_t* status /*[dev]*/, rgnn_stream_t stream);
+
+/* ================================================================ clustering (csrc/cluster.hip)
+ * DBSCAN labels of every frame of a batch over the rows of the radius search -- what sklearn.cluster.DBSCAN(eps, min_samples,
+ * algorithm="kd_tree").fit(points of the frame) returns in labels_ and core_sample_indices_, entry for entry, when rowptr / col are
+ * the rows of rgnn_radius_graph_rows at r = eps.  No reference counterpart (the RadarScenes baselines cluster on the host).
+ * Inputs ([dev]): rowptr int32 [n + 1], col int32 [n_edges] (global row ids; the search writes them ascending per row, the kernel does
+ * not rely on the order), frame_ptr int64 [n_frames + 1] (frame f = rows [frame_ptr[f], frame_ptr[f + 1])), group int32 [n] or NULL.
+ * The rule, per frame, without any tolerance:
+ *   neighbourhood  S_i = the entries j of row i with j != i, j in i's frame and group[j] == group[i]; a point with group < 0 takes no
+ *                  part (label -1, not core, nobody's neighbour).  NULL: one group per frame.
+ *   core           |S_i| + 1 >= min_samples (min_samples counts the point itself, as in scikit-learn).
+ *   cluster        a connected component of the core points under the edges between two core points (an entry (i, j) joins i and j,
+ *                  whether or not row j lists i); its root is its smallest row.
+ *   numbering      the clusters of a frame are numbered 0, 1, ... by ascending root, across groups; every frame starts at 0.
+ *   labels         core: the cluster's number; not core with a core neighbour: the smallest number among its core neighbours; else -1.
+ * Outputs ([dev]): labels int32 [n], core uint8 [n] (0 / 1), n_clusters int32 [n_frames]; *status gets the bits below (the caller
+ * zeroes it).  One launch, one work-group per frame, the frame's union-find array in LDS (4 bytes per point, 96 KB): a frame of more
+ * than rgnn_dbscan_max_frame_points() (24 576) points raises RGNN_STATUS_DBSCAN_FRAME_TOO_LARGE, its rows get label -1 and core 0
+ * and its n_clusters 0; the other frames are written as usual.  There is no path through global memory for larger frames: no
+ * work-group ever reads what another wrote in the same launch.  An entry of col outside its row's frame is skipped, a row whose
+ * offsets leave [0, n_edges] counts as empty, a frame outside [0, n] is left unwritten (n_clusters 0); each raises
+ * RGNN_STATUS_DBSCAN_BAD_ROW and is never used as an index.  Every loop is bounded by the frame's size or a row's length; convergence
+ * is never decided on the host.  The result is a function of the inputs alone (no floating-point work, no order-dependent atomics). */
+int32_t rgnn_dbscan_max_frame_points(void);
+int rgnn_dbscan_labels(const int32_t* rowptr, const int32_t* col, int64_t n, int64_t n_edges, const int64_t* frame_ptr,
+                       int64_t n_frames, int32_t min_samples, const int32_t* group /*[dev] or NULL*/, int32_t* labels, uint8_t* core,
+                       int32_t* n_clusters, int32_t* status /*[dev]*/, rgnn_stream_t stream);
+
+/* Class scores of clusters: cluster o owns the point rows obj_rows[obj_ptr[o] .. obj_ptr[o + 1]) (the CSR of the Python layer's
+ * group_objects; int64 [n_obj + 1], int32 [n_rows]); prob: float32 [n, n_classes] with row stride ldp.  mean[o, k] (float64
+ * [n_obj, n_classes]) = the mean of prob[row, k] over the members, summed in float64 in a fixed order (one wave per cluster: lane l
+ * adds the members l, l + 64, ... in that order, then a xor butterfly over the lanes), so the same input gives the same bits.
+ * per_class != 0: cls[o] = group[first member] (group int32 [n], required), score[o] = mean[o, cls[o]] (NaN if that is no column).
+ * per_class == 0: cls[o] = the k != bg_index with the largest mean, the lowest k on ties (-1 and NaN if there is none).
+ * Rows outside [0, n) are left out of the mean; a cluster without members gets NaN means. */
+int rgnn_cluster_scores(const float* prob, int64_t ldp, int32_t n_classes, int64_t n, const int64_t* obj_ptr, const int32_t* obj_rows,
+                        int64_t n_rows, int64_t n_obj, const int32_t* group /*[dev] or NULL*/, int32_t bg_index, int32_t per_class,
+                        double* mean, int32_t* cls, double* score, rgnn_stream_t stream);
 
 /* ---------------------------------------------------------------- point-cloud frames of a sequence (csrc/preprocess.hip)
  * create_point_cloud_frames + SceneCollection.process + PointCloudProcessor.transform (preprocessor/radarscenes/

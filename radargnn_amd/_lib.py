@@ -192,6 +192,9 @@ SIGNATURES = {
     "rgnn_stage_frames": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_i64]),
     "rgnn_gt_object_cap": (c_i32, []),
     "rgnn_create_gt_boxes": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_dbscan_max_frame_points": (c_i32, []),
+    "rgnn_dbscan_labels": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_cluster_scores": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rgnn_accumulate_frames_tmp_bytes": (c_i64, [c_i64]),
     "rgnn_accumulate_frames": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_i32,
                                        c_i32, c_f64, c_f64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -193,6 +193,8 @@ STATUS_GT_DEGENERATE_OBJECT = 128
 STATUS_PREPROCESS_BAD_ROW = 256
 STATUS_NUSC_BAD_CHUNK = 512
 STATUS_NUSC_BAD_BOX_PTR = 1024
+STATUS_DBSCAN_FRAME_TOO_LARGE = 2048
+STATUS_DBSCAN_BAD_ROW = 4096
 SPLITK_TIMEOUT_WORD = 1000          # rgnn.h RGNN_SPLITK_TIMEOUT_WORD
 
 
@@ -2111,6 +2113,69 @@ def create_gt_boxes(pos: torch.Tensor, obj_ptr: torch.Tensor, obj_rows: torch.Te
     check(lib.rgnn_create_gt_boxes(_ptr(pos), n, _ptr(obj_ptr), _ptr(obj_rows), obj_rows.numel(), n_obj, _ptr(nn_index),
                                    1 if aligned else 0, int(invariance), _ptr(out), _ptr(rect), _ptr(status), _stream()))
     return out, rect, status
+
+
+# ---- clustering (csrc/cluster.hip) -----------------------------------------------------------------------------------
+def dbscan_max_frame_points() -> int:
+    """Points of one frame ``dbscan_labels`` clusters (rgnn_dbscan_max_frame_points): the frame's union-find array lives in LDS."""
+    return int(lib.rgnn_dbscan_max_frame_points())
+
+
+def dbscan_labels(rowptr: torch.Tensor, col: torch.Tensor, frame_ptr: torch.Tensor, min_samples: int,
+                  group: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None):
+    """DBSCAN labels of every frame over the rows of a radius search (rgnn_dbscan_labels, the rule in rgnn.h): ``rowptr`` int32
+    [N + 1], ``col`` int32 [E] (``radius_graph`` at r = eps, or ``GraphBatch.rowptr`` / ``edge_index[1]`` as int32), ``frame_ptr``
+    int64 [B + 1], ``group`` int32 [N] or None (negative: the point takes no part; edges between groups do not exist).
+    -> (labels int32 [N], core uint8 [N], n_clusters int32 [B], status int32 [1]).  One launch, no host read: the caller reads
+    ``status`` (STATUS_DBSCAN_FRAME_TOO_LARGE: a frame above ``dbscan_max_frame_points()``, its rows are -1; STATUS_DBSCAN_BAD_ROW)."""
+    _dev(rowptr, "rowptr", torch.int32), _dev(col, "col", torch.int32), _dev(frame_ptr, "frame_ptr", torch.int64)
+    if rowptr.dim() != 1 or rowptr.numel() < 1 or col.dim() != 1 or frame_ptr.dim() != 1 or frame_ptr.numel() < 1:
+        raise ValueError("shapes: rowptr [N + 1], col [E], frame_ptr [B + 1]")
+    if isinstance(min_samples, bool) or not isinstance(min_samples, numbers.Integral) or not 1 <= int(min_samples) < 2 ** 31:
+        raise ValueError(f"min_samples must be an integer in [1, 2^31) (got {min_samples!r})")
+    n, b, dev = rowptr.numel() - 1, frame_ptr.numel() - 1, rowptr.device
+    if group is not None:
+        _dev(group, "group", torch.int32)
+        if group.shape != (n,):
+            raise ValueError("group must be [N]")
+        group = group.contiguous()
+    rowptr, col, frame_ptr = rowptr.contiguous(), col.contiguous(), frame_ptr.contiguous()
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    core = torch.empty(n, dtype=torch.uint8, device=dev)
+    n_clusters = torch.empty(b, dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib.rgnn_dbscan_labels(_ptr(rowptr), _ptr(col), n, col.numel(), _ptr(frame_ptr), b, int(min_samples), _ptr(group),
+                                 _ptr(labels), _ptr(core), _ptr(n_clusters), _ptr(status), _stream()))
+    return labels, core, n_clusters, status
+
+
+def cluster_scores(prob: torch.Tensor, obj_ptr: torch.Tensor, obj_rows: torch.Tensor, bg_index: int,
+                   group: Optional[torch.Tensor] = None, per_class: bool = False):
+    """Class scores of clusters (rgnn_cluster_scores): ``prob`` f32 [N, K]; ``obj_ptr`` / ``obj_rows``: ``group_objects``.
+    -> (mean f64 [M, K], the members' mean class probabilities summed in float64 in a fixed order; cls int32 [M]; score f64 [M]).
+    ``per_class``: cls is ``group`` (int32 [N]) at the cluster's first member, score the mean of that column; otherwise cls is the
+    argmax of the means over k != bg_index (lowest k on ties) and score that mean."""
+    prob = _rowmajor(_dev(prob, "prob", torch.float32), "prob")
+    _dev(obj_ptr, "obj_ptr", torch.int64), _dev(obj_rows, "obj_rows", torch.int32)
+    if obj_ptr.dim() != 1 or obj_ptr.numel() < 1 or obj_rows.dim() != 1 or prob.shape[1] < 1:
+        raise ValueError("shapes: prob [N, K] with K >= 1, obj_ptr [M + 1], obj_rows 1-D")
+    n, k = prob.shape
+    m, dev = obj_ptr.numel() - 1, prob.device
+    if per_class and group is None:
+        raise ValueError("per_class needs `group`")
+    if group is not None:
+        _dev(group, "group", torch.int32)
+        if group.shape != (n,):
+            raise ValueError("group must be [N]")
+        group = group.contiguous()
+    obj_ptr, obj_rows = obj_ptr.contiguous(), obj_rows.contiguous()
+    mean = torch.empty((m, k), dtype=torch.float64, device=dev)
+    cls = torch.empty(m, dtype=torch.int32, device=dev)
+    score = torch.empty(m, dtype=torch.float64, device=dev)
+    check(lib.rgnn_cluster_scores(_ptr(prob), _ld(prob), k, n, _ptr(obj_ptr), _ptr(obj_rows), obj_rows.numel(), m, _ptr(group),
+                                  int(bg_index), 1 if per_class else 0, _ptr(mean), _ptr(cls), _ptr(score), _stream()))
+    return mean, cls, score
 
 
 def accumulate_frames(columns: dict, win_rows: torch.Tensor, sensor_yaw: torch.Tensor, label_map: torch.Tensor, crop: bool,
