@@ -1285,6 +1285,62 @@ int rgnn_rigid_graph_edges(const float* edge_attr, int64_t lda, const int32_t* e
                            int64_t n_graphs, const double* angle, const float* pos, const float* vel, float* out, int64_t ldo,
                            rgnn_stream_t stream);
 
+/* ---------------------------------------------------------------- subgraphs (csrc/subgraph.hip)
+ * A part of a collated batch: the nodes i with keep_nodes[i] != 0 and the edges e = (s, t) with keep_edges[e] != 0 whose two ends are
+ * kept, in their order, relabelled (PyG: torch_geometric.utils.subgraph with relabel_nodes, dropout_node, dropout_edge; no reference
+ * counterpart).  edge_index int64 [2, E] (row stride E), batch int64 [N] = the graph of every node, ptr int64 [B + 1] = the node
+ * offsets, keep_nodes uint8 [N] or NULL (all), keep_edges uint8 [E] or NULL (all); N + E + 1 < 2^31 (else
+ * RGNN_ERR_INVALID_ARGUMENT).  The count -> scan -> fill protocol, every buffer the caller's:
+ *   rgnn_subgraph_flags      flags int32 [N + E]: flags[i] = node i is kept, flags[N + e] = edge e is kept; graph_edges int32 [B],
+ *                            ZEROED BY THE CALLER: the kept edges of every graph (of their source's graph); one launch;
+ *   rgnn_exclusive_scan_i32  scan int32 [N + E + 1] of flags: new_id[i] = flags[i] ? scan[i] : -1 is the relabelling, a kept edge e
+ *                            goes to place scan[N + e] - scan[N];
+ *   rgnn_subgraph_offsets    ptr_out int64 [B + 1]: ptr_out[g] = scan[ptr[g]], the kept nodes of the graphs before g; edge_ptr_out
+ *                            int64 [B + 1]: the kept edges whose source lies in a graph before g; totals int32 [4] = {N', E', the
+ *                            status word as it stands, 0} -- the caller sizes the outputs AND learns of bad input by ONE 16-byte
+ *                            host read, the only one of the operation; one launch of one work-group;
+ *   rgnn_subgraph_fill       edge_index_out int64 [2, E'] (row stride E') = (new_id[s], new_id[t]), batch_out int64 [N'] = batch of the
+ *                            kept nodes, new_id int32 [N], node_ids int64 [N'] / edge_ids int64 [E'] = the original positions; any
+ *                            output may be NULL; n_out = N', e_out = E' as read (a place outside them is not written); one launch;
+ *   rgnn_subgraph_gather_rows  out[r, :] = src[ids[r], :] for r < n_out: rows of `width` 4-byte words, row stride ld_src words in
+ *                            src, `width` in out; ids as node_ids / edge_ids; 16 bytes per lane when width and ld_src are
+ *                            multiples of 4 and both bases 16-byte aligned, else one word per lane; one launch per attribute.
+ * Every index is range-checked before it is used as one.  An edge is dropped, whatever the masks say, and its bit is raised in
+ * `status`, when an end lies outside [0, N) (BAD_ENDPOINT), the graph of its source lies outside [0, B) (BAD_GRAPH), its ends
+ * lie in two graphs (CROSS_GRAPH), or the source of the edge before it is a node of a LATER graph (EDGE_ORDER: the edge list of a
+ * collated batch is grouped by graph, ascending; the first edge of every descent is the one dropped).  A ptr[g] outside [0, N] is
+ * clamped and raises BAD_GRAPH.  An id outside [0, n_in) leaves its row of the gather unwritten.
+ * No kernel waits on another work-group, every loop is bounded by a shape or the wave size, the atomics are integer adds and ors
+ * (the result does not depend on scheduling), and no input is ever written.
+ *
+ * rgnn_edge_pair_mask: mask_out[e] uint8 = keep edge e, decided by the UNORDERED pair of its ends so that (s, t) and (t, s) fall
+ * together (DropEdge on symmetric and undirected graphs).  With lo = min(s, t), hi = max(s, t), arithmetic mod 2^64 and
+ *   mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)
+ * draw = mix(mix(seed) ^ ((lo << 32) | hi)) >> 40 (24 bits) and keep = draw >= threshold, threshold = floor(p 2^24) in [0, 2^24]:
+ * p = 0 keeps every edge, p = 1 none.  seed: [dev] int64 [1], never read by the host.  An edge with an end outside [0, N) gets 0;
+ * N <= 2^32.  One launch.
+ *
+ * rgnn_store_degree_column: x[i, column] = (float)degree[i] for i < n (x float32, row stride ldx): the `degree` node feature
+ * rewritten after rgnn_undirected_degree on the kept graph.  One launch. */
+#define RGNN_STATUS_SUBGRAPH_BAD_ENDPOINT 8192
+#define RGNN_STATUS_SUBGRAPH_CROSS_GRAPH 16384
+#define RGNN_STATUS_SUBGRAPH_EDGE_ORDER 32768
+#define RGNN_STATUS_SUBGRAPH_BAD_GRAPH 65536
+int rgnn_subgraph_flags(const int64_t* edge_index, int64_t n_edges, const int64_t* batch, int64_t n, int64_t n_graphs,
+                        const uint8_t* keep_nodes /*[dev] or NULL*/, const uint8_t* keep_edges /*[dev] or NULL*/, int32_t* flags,
+                        int32_t* graph_edges, int32_t* status, rgnn_stream_t stream);
+int rgnn_subgraph_offsets(const int32_t* scan, const int32_t* graph_edges, const int64_t* ptr, int64_t n, int64_t n_edges,
+                          int64_t n_graphs, int64_t* ptr_out, int64_t* edge_ptr_out, int32_t* totals, int32_t* status,
+                          rgnn_stream_t stream);
+int rgnn_subgraph_fill(const int64_t* edge_index, int64_t n_edges, const int64_t* batch, int64_t n, const int32_t* flags,
+                       const int32_t* scan, int64_t n_out, int64_t e_out, int64_t* edge_index_out, int64_t* batch_out,
+                       int32_t* new_id, int64_t* node_ids, int64_t* edge_ids, rgnn_stream_t stream);
+int rgnn_subgraph_gather_rows(const void* src, int64_t ld_src, int32_t width, const int64_t* ids, int64_t n_out, int64_t n_in,
+                              void* out, rgnn_stream_t stream);
+int rgnn_edge_pair_mask(const int64_t* edge_index, int64_t n_edges, int64_t n, const int64_t* seed /*[dev] int64 [1]*/,
+                        int32_t threshold, uint8_t* mask_out, rgnn_stream_t stream);
+int rgnn_store_degree_column(const int32_t* degree, int64_t n, float* x, int64_t ldx, int32_t column, rgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

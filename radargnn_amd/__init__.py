@@ -8,7 +8,8 @@ Sub-modules
     radargnn_amd.frames              batched on-device pipeline: frames in HBM -> graphs -> logits / boxes
     radargnn_amd.preprocessor        a RadarScenes sequence's detection table -> point-cloud frames, graphs and targets in HBM
     radargnn_amd.clustering          batched DBSCAN over the radius search's rows; clusters of a segmented cloud as boxes / detections
-    radargnn_amd.synthetic           deterministic synthetic radar frames (no dataset travels with the repo)
+    radargnn_amd.subgraph            parts of a resident batch: node and edge masks, node and edge dropout, point dropout of frames
+    radargnn_amd.synthetic         deterministic synthetic radar frames (no dataset travels with the repo)
     radargnn_amd.checkpoint          reads the reference trainer's whole-module pickles without torch_geometric
 
 There is no CPU fallback: importing ``radargnn_amd.ops`` without the built ``librgnn.so`` raises.
@@ -18,9 +19,9 @@ __version__ = "0.1.0"
 
 def __getattr__(name):
     # `radargnn_amd.clustering` without an import of its own (it needs the built library: resolved on first use, like every sub-module)
-    if name == "clustering":
+    if name in ("clustering", "subgraph"):
         import importlib
-        return importlib.import_module(".clustering", __name__)
+        return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -223,6 +223,12 @@ SIGNATURES = {
                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "rgnn_rigid_graph_edges": (c_i32, [c_vp, c_i64, C.POINTER(c_i32), c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp,
                                        c_vp, c_i64, c_vp]),
+    "rgnn_subgraph_flags": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_subgraph_offsets": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_subgraph_fill": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rgnn_subgraph_gather_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
+    "rgnn_edge_pair_mask": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp]),
+    "rgnn_store_degree_column": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp]),
 }
 
 

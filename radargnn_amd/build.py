@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "librgnn.so")
-SOURCES = ["core.hip", "graph.hip", "features.hip", "linear.hip", "linear_dma.hip", "mpnn.hip", "mpnn_tiles.hip", "norm.hip", "backward.hip", "wgrad.hip", "collate.hip", "postprocess.hip", "evaluate.hip", "metrics.hip", "loss.hip", "embed.hip", "groundtruth.hip", "preprocess.hip", "nuscenes.hip", "nuscenes_eval.hip", "optim.hip", "transform.hip", "cluster.hip"]
+SOURCES = ["core.hip", "graph.hip", "features.hip", "linear.hip", "linear_dma.hip", "mpnn.hip", "mpnn_tiles.hip", "norm.hip", "backward.hip", "wgrad.hip", "collate.hip", "postprocess.hip", "evaluate.hip", "metrics.hip", "loss.hip", "embed.hip", "groundtruth.hip", "preprocess.hip", "nuscenes.hip", "nuscenes_eval.hip", "optim.hip", "transform.hip", "cluster.hip", "subgraph.hip"]
 # per-file flags.  mpnn_tiles.hip: its running maxima take MFMA results; without -fno-honor-nans hipcc quiets every operand of
 # every fmaxf with a `v_max_f32 x, x, x` of its own (twice the vector instructions of the segmented maximum)
 EXTRA_FLAGS = {"mpnn_tiles.hip": ["-fno-honor-nans"]}

@@ -195,6 +195,10 @@ STATUS_NUSC_BAD_CHUNK = 512
 STATUS_NUSC_BAD_BOX_PTR = 1024
 STATUS_DBSCAN_FRAME_TOO_LARGE = 2048
 STATUS_DBSCAN_BAD_ROW = 4096
+STATUS_SUBGRAPH_BAD_ENDPOINT = 8192
+STATUS_SUBGRAPH_CROSS_GRAPH = 16384
+STATUS_SUBGRAPH_EDGE_ORDER = 32768
+STATUS_SUBGRAPH_BAD_GRAPH = 65536
 SPLITK_TIMEOUT_WORD = 1000          # rgnn.h RGNN_SPLITK_TIMEOUT_WORD
 
 
@@ -2176,6 +2180,125 @@ def cluster_scores(prob: torch.Tensor, obj_ptr: torch.Tensor, obj_rows: torch.Te
     check(lib.rgnn_cluster_scores(_ptr(prob), _ld(prob), k, n, _ptr(obj_ptr), _ptr(obj_rows), obj_rows.numel(), m, _ptr(group),
                                   int(bg_index), 1 if per_class else 0, _ptr(mean), _ptr(cls), _ptr(score), _stream()))
     return mean, cls, score
+
+
+# ---- subgraphs (csrc/subgraph.hip) -----------------------------------------------------------------------------------
+def keep_mask(mask: Optional[torch.Tensor], count: int, name: str) -> Optional[torch.Tensor]:
+    """A bool / uint8 mask [count] on the device as the uint8 array the kernels read (a bool tensor is viewed, not copied)."""
+    if mask is None:
+        return None
+    _dev(mask, name)
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"`{name}` must be a bool or uint8 mask, got {mask.dtype}")
+    if mask.shape != (count,):
+        raise ValueError(f"`{name}` must hold one entry per row: [{count}], got {tuple(mask.shape)}")
+    mask = mask.contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def subgraph_structure(edge_index: Optional[torch.Tensor], batch: Optional[torch.Tensor], ptr: torch.Tensor, n: int,
+                       keep_nodes: Optional[torch.Tensor] = None, keep_edges: Optional[torch.Tensor] = None,
+                       want_new_id: bool = False) -> dict:
+    """The structure of a part of a batch (rgnn_subgraph_flags -> rgnn_exclusive_scan_i32 -> rgnn_subgraph_offsets ->
+    rgnn_subgraph_fill, the rules in rgnn.h): ``edge_index`` int64 [2, E] and ``batch`` int64 [n] (both None: rows without edges,
+    a ``FrameBatch``), ``ptr`` int64 [B + 1], the masks as ``keep_mask`` returns them.
+    -> dict: ``edge_index`` int64 [2, E'] relabelled, ``batch`` int64 [N'], ``ptr`` / ``edge_ptr`` int64 [B + 1], ``node_ids`` int64
+    [N'] / ``edge_ids`` int64 [E'] (the original positions, ascending: what ``gather_rows_by_id`` takes), ``new_id`` int32 [n]
+    (-1: dropped) when asked for, ``status`` (an int: the STATUS_SUBGRAPH_* bits).
+    Between the offsets and the fill the host reads 16 bytes -- N', E' and the status word -- to size the outputs: the ONE host
+    read (and synchronisation) of the operation."""
+    _dev(ptr, "ptr", torch.int64)
+    dev = ptr.device
+    b = ptr.numel() - 1
+    if ptr.dim() != 1 or b < 0:
+        raise ValueError("ptr must be [B + 1]")
+    if edge_index is None:
+        ei, e = None, 0
+    else:
+        _dev(edge_index, "edge_index", torch.int64)
+        if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+            raise ValueError("edge_index must be [2, E]")
+        ei, e = edge_index.contiguous(), edge_index.shape[1]
+    if batch is not None:
+        _dev(batch, "batch", torch.int64)
+        if batch.shape != (n,):
+            raise ValueError(f"batch must be [{n}]")
+        batch = batch.contiguous()
+    elif e:
+        raise ValueError("edges need the batch vector")
+    if n + e + 1 >= 2 ** 31:
+        raise ValueError(f"N + E + 1 = {n + e + 1} does not fit the int32 scan (must stay below 2^31)")
+    ptr = ptr.contiguous()
+    ws = torch.zeros(b + 5, dtype=torch.int32, device=dev)          # kept edges per graph [b] | status [1] | totals [4]
+    graph_edges, status, totals = ws[:b], ws[b:b + 1], ws[b + 1:]
+    flags = torch.empty(n + e, dtype=torch.int32, device=dev)
+    check(lib.rgnn_subgraph_flags(_ptr(ei), e, _ptr(batch), n, b, _ptr(keep_nodes), _ptr(keep_edges), _ptr(flags), _ptr(graph_edges),
+                                  _ptr(status), _stream()))
+    scan = exclusive_scan_i32(flags)
+    offsets = torch.empty((2, b + 1), dtype=torch.int64, device=dev)
+    check(lib.rgnn_subgraph_offsets(_ptr(scan), _ptr(graph_edges), _ptr(ptr), n, e, b, _ptr(offsets[0]), _ptr(offsets[1]), _ptr(totals),
+                                    _ptr(status), _stream()))
+    n_out, e_out, bits, _ = (int(v) for v in totals.cpu())         # the one host read
+    out = {"ptr": offsets[0], "edge_ptr": offsets[1], "status": bits,
+           "edge_index": torch.empty((2, e_out), dtype=torch.int64, device=dev) if ei is not None else None,
+           "batch": torch.empty(n_out, dtype=torch.int64, device=dev) if batch is not None else None,
+           "node_ids": torch.empty(n_out, dtype=torch.int64, device=dev),
+           "edge_ids": torch.empty(e_out, dtype=torch.int64, device=dev),
+           "new_id": torch.empty(n, dtype=torch.int32, device=dev) if want_new_id else None}
+    check(lib.rgnn_subgraph_fill(_ptr(ei), e, _ptr(batch), n, _ptr(flags), _ptr(scan), n_out, e_out, _ptr(out["edge_index"]),
+                                 _ptr(out["batch"]), _ptr(out["new_id"]), _ptr(out["node_ids"]), _ptr(out["edge_ids"]), _stream()))
+    return out
+
+
+def gather_rows_by_id(src: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """out[r] = src[ids[r]] (rgnn_subgraph_gather_rows): ``src`` [R, ...] of a dtype whose rows are whole 4-byte words (what
+    ``collate_rows`` moves), ``ids`` int64 [R'] inside [0, R).  A 2-D ``src`` may be a column slice (rows contiguous, any row
+    stride); anything else that is not contiguous is copied first.  Bit-exact; 16 bytes per lane when the rows allow it."""
+    _dev(src, "src"), _dev(ids, "ids", torch.int64)
+    if src.dim() < 1 or ids.dim() != 1:
+        raise ValueError("src must have a leading row dimension and ids must be 1-D")
+    width = _words_per_row(src)
+    src = _rowmajor(src, "src") if src.dim() == 2 else src.contiguous()
+    out = torch.empty((ids.numel(),) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    if width == 0 or ids.numel() == 0:
+        return out
+    ld = width if src.dim() != 2 else _ld(src) * src.element_size() // 4
+    if src.dim() == 2 and ((_ld(src) * src.element_size()) % 4 or src.data_ptr() % 4):     # 2-byte dtypes sliced at an odd column
+        src, ld = src.clone(memory_format=torch.contiguous_format), width
+    check(lib.rgnn_subgraph_gather_rows(_ptr(src), ld, width, _ptr(ids.contiguous()), ids.numel(), src.shape[0], _ptr(out), _stream()))
+    return out
+
+
+def pair_threshold(p: float) -> int:
+    """floor(p 2^24): the threshold ``edge_pair_mask`` compares its 24-bit draws with."""
+    if isinstance(p, bool) or not isinstance(p, numbers.Real) or not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"p must be a probability in [0, 1] (got {p!r})")
+    return int(math.floor(float(p) * (1 << 24)))
+
+
+def edge_pair_mask(edge_index: torch.Tensor, n: int, seed: torch.Tensor, p: float) -> torch.Tensor:
+    """Keep mask bool [E] of DropEdge with probability ``p``, decided by the UNORDERED pair of an edge's ends so that (s, t) and
+    (t, s) fall together (rgnn_edge_pair_mask: the hash is stated in rgnn.h).  ``seed``: int64 [1] on the device, never read back.
+    One launch, no host read."""
+    threshold = pair_threshold(p)
+    _dev(edge_index, "edge_index", torch.int64), _dev(seed, "seed", torch.int64)
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or seed.numel() != 1:
+        raise ValueError("edge_index must be [2, E] and seed one int64")
+    if not 0 <= int(n) <= 2 ** 32:
+        raise ValueError("n must lie in [0, 2^32]: node ids are packed into 32 bits")
+    ei = edge_index.contiguous()
+    mask = torch.empty(ei.shape[1], dtype=torch.uint8, device=ei.device)
+    check(lib.rgnn_edge_pair_mask(_ptr(ei), ei.shape[1], int(n), _ptr(seed.contiguous()), threshold, _ptr(mask), _stream()))
+    return mask.view(torch.bool)
+
+
+def store_degree_column(x: torch.Tensor, degree: torch.Tensor, column: int) -> torch.Tensor:
+    """x[:, column] = degree, in place, on a contiguous float32 [N, D] the caller owns (rgnn_store_degree_column)."""
+    _dev(x, "x", torch.float32), _dev(degree, "degree", torch.int32)
+    if x.dim() != 2 or not x.is_contiguous() or degree.shape != (x.shape[0],) or not 0 <= column < x.shape[1]:
+        raise ValueError("x must be contiguous [N, D], degree [N] and the column inside x")
+    check(lib.rgnn_store_degree_column(_ptr(degree.contiguous()), x.shape[0], _ptr(x), x.shape[1], int(column), _stream()))
+    return x
 
 
 def accumulate_frames(columns: dict, win_rows: torch.Tensor, sensor_yaw: torch.Tensor, label_map: torch.Tensor, crop: bool,
